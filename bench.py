@@ -7,8 +7,21 @@ convergence_diff -> batched subproblem solve), the body of ``PHBase.iterk_loop``
 it fits one MI355X), rho = 1, scenarios sharded contiguously over the ranks
 (strong scaling: the 100k total is fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run does what the headline figure needs and no more: it builds the
+objects, warms up, times Iter0 + K iterations, writes the timed run's outputs if
+--dump-outputs is given, and prints the result line.  --full adds everything
+listed under "Extra keys" below that takes a run of its own (the kernel-timing
+run behind ``roofline``, ``conv_time``, ``allreduce_hook``, ``cpu_baseline``,
+``configs``) and writes the full record to the --detail file.
+--dump-outputs DIR: what a caller of the timed path holds after its last
+iteration (x-bar, x-squared-bar, W, the subproblem solutions, objectives and
+statuses, conv, the trivial bound) as DIR/<name>.npy in float64; above DUMP_CAP
+bytes the per-scenario arrays keep a fixed seeded sample of the scenarios
+(``scenario_index.npy``).  The inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, this process launches
 the N ranks itself (torch.distributed.run, one process per GPU, 127.0.0.1
@@ -23,7 +36,8 @@ device: phx_iterk), bracketed by barrier + device synchronize (none in between:
 Iter0's share from events around it), MAX over ranks; K
 steps are timed, Iter0 counts as one more scenario-solve pass.  W warmup: a full
 untimed Iter0 + W iterations on a separate PH object first (JIT, allocator).
-Inputs resident in HBM before timing.  Extra keys:
+Inputs resident in HBM before timing.  Extra keys (steady always, the
+others with --full):
   steady        S K / T_iterk (Iter0 excluded) and the per-iteration time
   conv_time     wall time from Iter0 to conv < 1e-4 (convthresh 1e-4), iterations
   roofline      the dominant kernel of the timed iterations (phx_lane_warm):
@@ -65,6 +79,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also: the kernel-timing run (roofline), time to conv < 1e-4, the all-reduce hook probe, "
+                         "the CPU baselines, the other configs, and the --detail file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed run computed (after its last iteration) as DIR/<name>.npy")
     ap.add_argument("--build-after-warmup", action="store_true",
                     help="build the timed object after the warmup run (default: before it, so the warmup's "
                          "steps run right before the timed region)")
@@ -93,8 +112,9 @@ def parse():
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: test hook (gloo + the host emulation library, no GPU)")
     ap.add_argument("--so", default=None, help="extra solver options (JSON), e.g. '{\"seed_templates\": 0}'")
-    ap.add_argument("--detail", default=os.path.join(_ROOT, "bench_detail.json"),
-                    help="file for the full per-config record (stdout's last line is the compact headline)")
+    ap.add_argument("--detail", default=None,
+                    help="file for the full per-config record (stdout's last line is the compact headline); "
+                         "with --full it defaults to bench_detail.json beside this file")
     ap.add_argument("--ar-probe", type=int, default=1,
                     help="N = 1: time phx_iterk with a no-op all-reduce callback (the per-iteration host "
                          "cost of the Python collective hook)")
@@ -451,6 +471,46 @@ def final_state(ph):
             "trivial_bound": ph.trivial_bound}
 
 
+DUMP_CAP = 64 * 1000 * 1000     # bytes of .npy data one --dump-outputs writes, at most
+
+
+def dump_outputs(ph, outdir, write=True):
+    """What a caller holds after the timed run's last iteration, as outdir/<name>.npy
+    (float64): x-bar and x-squared-bar (the nodes' slices concatenated in node
+    order), conv, the trivial bound, and per local scenario (rows in scenario
+    order) W, the nonant values, the whole solution x, the objective and the
+    solve status.  If the per-scenario arrays would not fit DUMP_CAP, they keep
+    the rows of a fixed sample of the scenarios (RandomState(0), sorted), which
+    scenario_index.npy lists."""
+    def f64(a):
+        return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+    def scalar(v):
+        return f64([np.nan if v is None else float(v)])
+
+    xb = ph.xbar_by_node()
+    out = {"xbar": f64(np.concatenate([a[0] for a in xb.values()])),
+           "xsqbar": f64(np.concatenate([a[1] for a in xb.values()])),
+           "conv": scalar(ph.conv), "trivial_bound": scalar(ph.trivial_bound)}
+    rows = {"W": ph.W_array(), "nonants": ph.nonant_values(), "x": ph._host("x").T,
+            "obj": ph._host("obj"), "status": ph._host("status")}
+    S = rows["obj"].shape[0]
+    # 128 bytes of .npy header per file, 8 per row for scenario_index
+    row_bytes = 8 + sum(8 * int(np.prod(a.shape[1:], dtype=np.int64)) for a in rows.values())
+    budget = DUMP_CAP - sum(a.nbytes for a in out.values()) - 128 * (len(out) + len(rows) + 1)
+    idx = np.arange(S)
+    if S * row_bytes > budget:
+        idx = np.sort(np.random.RandomState(0).choice(S, size=max(1, budget // row_bytes), replace=False))
+    out["scenario_index"] = f64(idx)
+    for k, a in rows.items():
+        out[k] = f64(a[idx])
+    if write:
+        os.makedirs(outdir, exist_ok=True)
+        for k, a in out.items():
+            np.save(os.path.join(outdir, k + ".npy"), a)
+    return out
+
+
 def ar_probe(w, S, cm, rho, so, K, dev):
     """Host cost of the Python all-reduce hook of phx_iterk: the same K iterations
     on one rank with and without a no-op callback installed (the multi-rank path
@@ -706,21 +766,28 @@ def main():
     st = getattr(ph, "iterk_stats", None)
     if st is not None and (st["iters"] != K or st["solves"] != K):
         raise RuntimeError("timed iterk_loop did not run %d full iterations: %s" % (K, st))
-    if ktim:
+    if args.dump_outputs:
+        dump_outputs(ph, args.dump_outputs, write=rank == 0)
+    # the dominant kernel's timing: a second timed run (--full), or the metric's
+    # own run where its events were recorded there (--kernel-timing-inline)
+    roof = None
+    if ktim and args.full:
         phk = make_ph(hl, S, cm, args.rho, so, K, dev)
         dev.sync()
         timed_run(phk, K, dev)
-        kernel, avg_s, launches, bpu, units = dominant_kernel(phk, K, args.fused)
+        roof = dominant_kernel(phk, K, args.fused)
         del phk
-    else:
-        kernel, avg_s, launches, bpu, units = dominant_kernel(ph, K, args.fused)
+    elif not ktim and (args.full or args.timing_every != 0):
+        roof = dominant_kernel(ph, K, args.fused)
     b = ph.batch
-    if world != 1:
+    if roof is None:
+        traffic, tsrc, tstat = None, None, None
+    elif world != 1:
         traffic, tsrc, tstat = None, None, "N > 1: per-rank PMC not collected"
     elif args.only is not None:
-        traffic, tsrc, tstat = pmc_traffic(kernel, CONFIG_PMC_TAG.get(args.only, args.only))
+        traffic, tsrc, tstat = pmc_traffic(roof[0], CONFIG_PMC_TAG.get(args.only, args.only))
     else:
-        traffic, tsrc, tstat = (pmc_traffic(kernel, "farmer100k") if S == 100000 and cm == 1
+        traffic, tsrc, tstat = (pmc_traffic(roof[0], "farmer100k") if S == 100000 and cm == 1
                                 else (None, None, "no PMC summary for this size"))
     nbad = sum(s.get("not_optimal", 0) for s in ph.solve_stats) + (st.get("not_optimal", 0) if st else 0)
     res = {
@@ -743,11 +810,11 @@ def main():
                    "parallelism": "scenario-sharded x%d, RCCL allreduce" % world},
         "T_s": T, "iter0_s": T0,
         "steady": {"value": S * K / Tk, "ms_per_step": Tk * 1e3 / K, "def": "S K / T_iterk (Iter0 excluded)"},
-        "roofline": dict(roofline(kernel, avg_s, launches, bpu, units, traffic, tsrc, tstat),
-                         valu=valu_issue(kernel, "farmer100k", units, avg_s, simds=simds())
+        "roofline": dict(roofline(*roof, traffic, tsrc, tstat),
+                         valu=valu_issue(roof[0], "farmer100k", roof[4], roof[1], simds=simds())
                          if (world == 1 and args.only is None and S == 100000 and cm == 1) else None,
                          timing_run=("a second timed run of the same K (the metric's run records no events)"
-                                     if ktim else "the metric's run")),
+                                     if ktim else "the metric's run")) if roof else None,
         "loop": ("PHBase.iterk_loop -> phx_iterk (device-driven, depth %d%s)"
                  % (args.depth, ", fused" if st and st.get("fused") else "")) if st else "PHBase host loop",
         "not_optimal": nbad, "setup_s": t_setup, "warmup_s": t_warm,
@@ -761,7 +828,7 @@ def main():
     del ph
     dev.empty_cache()
     # ---- time to conv < 1e-4 from Iter0 (fresh object, same data) ----
-    if not args.no_conv:
+    if args.full and not args.no_conv:
         ph2 = make_ph(hl, S, cm, args.rho, so_metric, args.conv_max_iters, dev, convthresh=1e-4)
         dev.sync()
         with no_gc():                       # (as the timed run)
@@ -776,13 +843,13 @@ def main():
         del ph2
         dev.empty_cache()
     # ---- host cost of the Python all-reduce hook (one rank) ----
-    if world == 1 and args.only is None and args.ar_probe:
+    if args.full and world == 1 and args.only is None and args.ar_probe:
         res["allreduce_hook"] = ar_probe(hl, S, cm, args.rho, so, K, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.only is None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.only is None:
         res["cpu_baseline"] = cpu_baseline(args, cm=cm)
         args._headline_cpu = res["cpu_baseline"]
     # ---- the other BASELINE configs (one GPU) ----
-    if world == 1 and args.only is None and args.configs != "none":
+    if args.full and world == 1 and args.only is None and args.configs != "none":
         names = (["C1", "C3s8", "C3x1M", "C2", "C4", "C5a", "C5b"] if args.configs == "all"
                  else args.configs.split(","))
         res["configs"] = {}
@@ -798,13 +865,16 @@ def main():
         # sample text) goes to a file; stdout's LAST line is the compact headline
         # the driver parses (<= LINE_CAP bytes; stderr stays short too: the
         # driver keeps only the tail of both)
-        full = json.dumps(res)
-        try:
-            with open(args.detail, "w") as f:
-                f.write(full + "\n")
-            print("[bench] full record: %s (%d bytes)" % (args.detail, len(full)), file=sys.stderr, flush=True)
-        except OSError as e:
-            print("[bench] could not write %s: %r" % (args.detail, e), file=sys.stderr, flush=True)
+        if args.detail is None and args.full:
+            args.detail = os.path.join(_ROOT, "bench_detail.json")
+        if args.detail is not None:
+            full = json.dumps(res)
+            try:
+                with open(args.detail, "w") as f:
+                    f.write(full + "\n")
+                print("[bench] full record: %s (%d bytes)" % (args.detail, len(full)), file=sys.stderr, flush=True)
+            except OSError as e:
+                print("[bench] could not write %s: %r" % (args.detail, e), file=sys.stderr, flush=True)
         print(json.dumps(compact_line(res, args.detail)), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -910,7 +980,8 @@ def compact_line(res, detail_path):
                                      if isinstance(cb, dict) and cb.get("spread") else None),
                       "stops": (cr.get("iterk") or {}).get("straggler_stops"), "not_optimal": cr.get("not_optimal")}
         out["configs"] = cs
-    out["detail"] = os.path.relpath(detail_path, _ROOT) if os.path.isabs(detail_path) else detail_path
+    if detail_path is not None:
+        out["detail"] = os.path.relpath(detail_path, _ROOT) if os.path.isabs(detail_path) else detail_path
     line = json.dumps(out)
     # shed the least important fields if the line ever outgrows the cap
     for drop in (("final",), ("iterk",), ("configs",)):

@@ -10,6 +10,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,7 +37,7 @@ def test_bench_line_compact_cpu(tmp_path):
     the CPU baseline, conv_time and a per-config summary; the full record goes to
     the --detail file."""
     detail = tmp_path / "detail.json"
-    d = _bench(1, extra=("--configs", "C1,C4", "--config-steps", "2", "--cpu-scens", "60", "--cpu-iters", "1",
+    d = _bench(1, extra=("--full", "--configs", "C1,C4", "--config-steps", "2", "--cpu-scens", "60", "--cpu-iters", "1",
                          "--cpu-procs", "2", "--conv-max-iters", "50"), tmp=detail)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "dtype", "config", "roofline",
               "cpu_baseline", "conv_time", "iter0_s", "steady", "configs"):
@@ -53,6 +54,73 @@ def test_bench_line_compact_cpu(tmp_path):
     full = json.loads(detail.read_text())
     assert full["configs"]["C4"]["workload"].startswith("aircond")
     assert full["value"] == d["value"] or abs(full["value"] - d["value"]) <= 1e-5 * full["value"]
+
+
+DUMPED = ["W", "conv", "nonants", "obj", "scenario_index", "status", "trivial_bound", "x", "xbar", "xsqbar"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_cpu(tmp_path):
+    """Without --full the run times its K steps and reports the headline alone: no
+    roofline run, conv_time, all-reduce probe, CPU baseline, other configs or detail
+    file.  --dump-outputs writes the timed run's final state as float64 .npy files,
+    the same from run to run."""
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = _bench(1, extra=("--dump-outputs", str(a)))
+    _bench(1, extra=("--dump-outputs", str(b)))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup",
+              "steady", "final"):
+        assert k in d, k
+    for k in ("cpu_baseline", "conv_time", "configs", "allreduce_hook", "detail"):
+        assert k not in d, k
+    assert d["roofline"] is None
+    assert d["steps"] == 3 and d["iterk"]["iters"] == 3
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(600 * 1e3 / d["ms_per_step"], rel=1e-4)
+    assert sorted(os.listdir(a)) == [n + ".npy" for n in DUMPED] == sorted(os.listdir(b))
+    got = {n: np.load(a / (n + ".npy")) for n in DUMPED}
+    for n, x in got.items():
+        assert x.dtype == np.float64, n
+        assert np.array_equal(x, np.load(b / (n + ".npy")), equal_nan=True), n
+    assert sum(x.nbytes for x in got.values()) <= 64e6
+    assert np.array_equal(got["scenario_index"], np.arange(600))
+    assert got["W"].shape == got["nonants"].shape == (600, 3) and got["x"].shape[0] == 600
+    assert got["obj"].shape == got["status"].shape == (600,)
+    assert np.allclose(got["xbar"], d["final"]["xbar"]["ROOT"], rtol=1e-12, atol=0)
+    assert got["conv"][0] == pytest.approx(d["final"]["conv"], rel=1e-12)
+    # W sums to zero over the (equally likely) scenarios; x-bar is the nonants' mean
+    assert np.abs(got["W"].sum(axis=0)).max() < 1e-6 * max(1.0, np.abs(got["W"]).max())
+
+
+def test_dump_outputs_samples_above_cap(tmp_path, monkeypatch):
+    """Per-scenario arrays that would not fit the cap keep a fixed sorted sample of
+    the scenarios (the same one every time), listed in scenario_index."""
+    import bench
+
+    class FakePH:
+        conv, trivial_bound, S = 0.5, None, 1000
+        x = np.arange(S * 7, dtype=np.float64).reshape(7, S)
+
+        def xbar_by_node(self):
+            return {"ROOT": (np.ones(3), 2 * np.ones(3))}
+
+        def W_array(self):
+            return -self.x[:3].T
+
+        def nonant_values(self):
+            return self.x[:3].T.copy()
+
+        def _host(self, key):
+            return {"x": self.x, "obj": self.x[6], "status": np.zeros(self.S, dtype=np.int32)}[key]
+
+    monkeypatch.setattr(bench, "DUMP_CAP", 20000)
+    out = bench.dump_outputs(FakePH(), str(tmp_path / "d"))
+    idx = out["scenario_index"].astype(int)
+    assert 100 < len(idx) < 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(out["x"], FakePH.x.T[idx]) and np.array_equal(out["W"], -FakePH.x[:3].T[idx])
+    assert np.isnan(out["trivial_bound"][0]) and out["conv"][0] == 0.5
+    files = os.listdir(tmp_path / "d")
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in files) <= 20000
+    again = bench.dump_outputs(FakePH(), None, write=False)
+    assert np.array_equal(again["scenario_index"], out["scenario_index"])
 
 
 def test_bench_launches_ranks_cpu():
