@@ -16,6 +16,13 @@ runs on hardware here:
 * the adopted Iter0's collective early exit: an infeasible scenario on rank 0
   only makes both ranks leave before any PH iteration (phbase.py:812-823).
 
+Two further cases run the host loop (``native_loop=0``: PHBase.Compute_Xbar,
+Update_W and convergence_diff, each with its own all-reduce) on several ranks:
+aircond [5,2,2] on 3 ranks, where no rank covers all 16 tree nodes and the
+one-block phx_xbar must return zeros for the absent ones, and farmer on
+2 x 1,000 scenarios (the one-block kernel's modes 1 and 2 under a real
+all-reduce).
+
 Each multi-rank run is checked against the one-process run of the same
 scenarios (conv_ranks = world size: the reference's per-rank normalisation,
 sputils.py:803-810 slices).  Tolerances: the ranks' x-bar sums add in another
@@ -33,12 +40,19 @@ import torch.multiprocessing as mp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STRAG = {"as_rounds": 1, "ipm_max_it": 3, "rescue_rounds": 1}
 CASES = {
-    # name: (model, world, S or branching factors, iterations, convthresh, fused, solver options)
-    "farmer-fused": ("farmer", 2, 2000, 60, 1.0, 1, None),
-    "farmer-unfused": ("farmer", 2, 2000, 60, 1.0, 0, None),
-    "farmer-strag-fused": ("farmer", 2, 2000, 8, 1e-10, 1, STRAG),
-    "farmer-strag-unfused": ("farmer", 2, 2000, 8, 1e-10, 0, STRAG),
-    "aircond3": ("aircond", 3, [5, 2, 2], 20, 1e-3, 1, None),
+    # name: (model, world, S or branching factors, iterations, convthresh, fused, solver options, native_loop)
+    "farmer-fused": ("farmer", 2, 2000, 60, 1.0, 1, None, 1),
+    "farmer-unfused": ("farmer", 2, 2000, 60, 1.0, 0, None, 1),
+    "farmer-strag-fused": ("farmer", 2, 2000, 8, 1e-10, 1, STRAG, 1),
+    "farmer-strag-unfused": ("farmer", 2, 2000, 8, 1e-10, 0, STRAG, 1),
+    "aircond3": ("aircond", 3, [5, 2, 2], 20, 1e-3, 1, None, 1),
+    # the host loop (PHBase.Compute_Xbar / Update_W / convergence_diff, each with
+    # its own all-reduce): every rank holds at most 1024 scenarios, so phx_xbar
+    # and phx_update_w take the one-block kernel; no aircond rank covers all 16
+    # tree nodes, so the node sums of absent nodes must come back zero from
+    # every phx_xbar call (the buffer is all-reduced in place)
+    "aircond3-host": ("aircond", 3, [5, 2, 2], 20, 1e-3, 0, None, 0),
+    "farmer-host": ("farmer", 2, 2000, 60, 1.0, 0, None, 0),
 }
 
 
@@ -54,8 +68,8 @@ def _run_case(case, lib, device, mpicomm=None, conv_ranks=None):
     from helpers import run_engine
     from mpisppy_amd.examples import aircond, farmer
     from mpisppy_amd.utils import sputils
-    model, world, size, iters, thresh, fused, so = CASES[case]
-    iterk = dict(so or {}, native_loop=1, iterk_fused=fused)
+    model, world, size, iters, thresh, fused, so, loop = CASES[case]
+    iterk = dict(so or {}, native_loop=loop, iterk_fused=fused)
     opts = {"convthresh": thresh, "iter0_solver_options": dict(so or {}), "iterk_solver_options": iterk}
     if conv_ranks:
         opts["conv_ranks"] = conv_ranks
@@ -69,7 +83,9 @@ def _run_case(case, lib, device, mpicomm=None, conv_ranks=None):
                                         {"branching_factors": size, "start_seed": 0}, iters, lib=lib,
                                         device=device, mpicomm=mpicomm, options=opts,
                                         all_nodenames=sputils.create_nodenames_from_branching_factors(size))
-    st = dict(ph.iterk_stats)
+    # (the host loop leaves no device-loop statistics)
+    st = dict(ph.iterk_stats) if loop else {"converged": ph._PHIter < iters,
+                                            "not_optimal": sum(s["not_optimal"] for s in ph.solve_stats)}
     st.pop("wall_s", None)
     st.pop("lane_warm_ms", None)
     return {"conv": conv, "Eobj": Eobj, "tb": tb, "W": ph.W_array(), "iters": ph._PHIter,
@@ -102,7 +118,7 @@ def _rel(a, b):
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("case", list(CASES))
 def test_ranks_match_one_gpu(gpu_lib, case):
-    model, world, size, iters, thresh, fused, so = CASES[case]
+    model, world, size, iters, thresh, fused, so, loop = CASES[case]
     # (a spawned manager: the parent holds a GPU context, which a forked
     # child must not inherit)
     mgr = mp.get_context("spawn").Manager()
@@ -117,7 +133,10 @@ def test_ranks_match_one_gpu(gpu_lib, case):
         st = r["stats"]
         # the multi-rank path ran on the device: fused where asked (two-stage, one
         # segment per rank), the same iteration count and stop as one process
-        assert st["fused"] == bool(fused and model == "farmer"), st
+        if loop:
+            assert st["fused"] == bool(fused and model == "farmer"), st
+        else:
+            assert "fused" not in st, st
         assert r["iters"] == one["iters"] and st["converged"] == one["stats"]["converged"], (st, one["stats"])
         assert st["not_optimal"] == 0
         if so:
