@@ -206,8 +206,20 @@ inline void emit_dtable(std::ostringstream& o, const char* name, const std::vect
     o << "}; return a[k]; }\n";
 }
 
-// HIP source of the specialised kernels `phx_lane_ipm` / `phx_lane_polish`
-// (hipRTC input).
+// The kernels of lane_kernel_source that the library loads, by exact symbol
+// name (phx_kernels.hip jit_compile fills LaneFns in this order; the host
+// emulation exports the list to tests/test_jit_source.py).
+enum LaneKernel {
+    LK_COLD, LK_COLD_AS, LK_WARM, LK_WARM_LIST, LK_MAP, LK_TAIL, LK_SEED, LK_WARM_FZ1, LK_WARM_FZR2, LK_ALL,
+    LK_LIST_ALL, LK_ALL_RL, LK_ALL_PK, LK_COUNT
+};
+constexpr const char* LANE_KERNEL_NAMES[] = {
+    "phx_lane_cold", "phx_lane_cold_as", "phx_lane_warm", "phx_lane_warm_list", "phx_lane_map", "phx_fz_tail",
+    "phx_lane_seed", "phx_lane_warm_fz1", "phx_lane_warm_fzr2", "phx_lane_all", "phx_lane_list_all",
+    "phx_lane_all_rl", "phx_lane_all_pk"};
+static_assert(sizeof(LANE_KERNEL_NAMES) / sizeof(LANE_KERNEL_NAMES[0]) == LK_COUNT, "one name per LaneKernel");
+
+// HIP source of the specialised lane-solver kernels (hipRTC input).
 // with_map: the warm kernels carry the affine-map paths (PHX_LANE_MAP=1);
 // without, that code is compiled out (fewer registers, no spills).
 inline std::string lane_kernel_source(const LaneStructure& L, int warm_waves = 1, bool with_map = false,
@@ -295,47 +307,30 @@ inline std::string lane_kernel_source(const LaneStructure& L, int warm_waves = 1
       << ") phx_lane_warm(phx_lane::LaneIO io) {\n"
          "  phx_lane::lane_stamp(io, 0);\n"
          "  if (phx_lane::gated(io.gate)) return;\n"
-         "  if (io.fz.on && !phx_lane::fz_prologue(io)) return;\n"
          "  phx_lane::zero_next_counts(io.counts_next);\n"
          "  phx_lane::lane_stamp(io, 1);\n"
          "  const int t = blockIdx.x * 64 + threadIdx.x;\n"
          "  bool still = false;\n"
          "  if (t < io.S) {\n"
-         "    if (io.fz.on) (void)phx_lane::fz_update_w<PT>(io, t);\n"
          "    phx_lane::lane_stamp(io, 2);\n"
          "    still = " + wl + "(io, t);\n"
          "  }\n"
          "  phx_lane::lane_stamp(io, 3);\n"
          "  phx_lane::compact_lane(still, t, io.lanes_out, io.count_out);\n"
          "  phx_lane::lane_stamp(io, 4);\n"
-         "  if (io.fz.on) phx_lane::fz_epilogue<PT>(io, t, still);\n"
          "  phx_lane::lane_stamp(io, 5);\n"
          "}\n";
     // phx_iterk fused mode: one whole PH iteration per launch, every load of
-    // the lane's Update_W and first round issued at entry (phx_lane.h warm_fused)
-    o << "extern \"C\" __global__ void __launch_bounds__(64, " << warm_waves
-      << ") phx_lane_warm_fz(phx_lane::LaneIO io) {\n"
-         "  phx_lane::warm_fused<PT>(io);\n"
-         "}\n";
-    // ... for batches of at most one wavefront per SIMD: the whole register
+    // the lane's Update_W and first round issued at entry (phx_lane.h warm_fused).
+    // For batches of at most one wavefront per SIMD: the whole register
     // file (VGPRs + AGPRs) for one wave, no scratch spills
     o << "extern \"C\" __global__ void __launch_bounds__(64, 1) phx_lane_warm_fz1(phx_lane::LaneIO io) {\n"
-         "#ifdef PHX_FZ1_RELOAD\n"
-         "  phx_lane::warm_fused<PT, false>(io);\n"
-         "#else\n"
-         "  phx_lane::warm_fused<PT, true>(io);\n"
-         "#endif\n"
+         "  phx_lane::warm_fused<PT>(io);\n"
          "}\n";
     // ... two waves per SIMD with every round on register data (above one
     // wavefront per SIMD; the compiler spills what does not fit 256 registers)
     o << "extern \"C\" __global__ void __launch_bounds__(64, 2) phx_lane_warm_fzr2(phx_lane::LaneIO io) {\n"
-         "  phx_lane::warm_fused<PT, true, PHX_FZR2_CARRY_DEF, PHX_FZR2_PARK_DEF>(io);\n"
-         "}\n";
-    // ... compacting: round 0 per lane, the later rounds of the lanes that need
-    // them packed into full wavefronts by each group's last block (phx_lane.h
-    // warm_fused_c)
-    o << "extern \"C\" __global__ void __launch_bounds__(64, 1) phx_lane_warm_fzc(phx_lane::LaneIO io) {\n"
-         "  phx_lane::warm_fused_c<PT>(io);\n"
+         "  phx_lane::warm_fused<PT, PHX_FZR2_CARRY_DEF, PHX_FZR2_PARK_DEF>(io);\n"
          "}\n";
     // a whole warm solve (warm rounds, rescue rounds, interior point) in one
     // launch, for batches of at most one wavefront per SIMD (phx_lane.h all_lane)

@@ -6,10 +6,12 @@ the GPU box, so a compile error there would only surface on the GPU.  The host
 emulation builds the same LaneStructure from the same setup code; here its
 source goes through hipRTC (libhiprtc, which needs no GPU) with the library's
 own options (phx_kernels.hip jit_compile), and every kernel the library loads
-must be present in the code object.
+(phx_jit.h LANE_KERNEL_NAMES, the list jit_compile looks up, exported by the
+emulation) must be a symbol of the code object, by its exact name.
 """
 import ctypes
 import os
+import struct
 
 import pytest
 
@@ -20,9 +22,6 @@ from mpisppy_amd.utils import sputils
 
 _CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mpi-sppy_amd", "csrc")
 _HIPRTC = "/opt/rocm/lib/libhiprtc.so"
-KERNELS = ["phx_lane_cold", "phx_lane_cold_as", "phx_lane_warm", "phx_lane_warm_list", "phx_lane_map",
-           "phx_fz_tail", "phx_lane_seed", "phx_lane_warm_fz", "phx_lane_warm_fz1", "phx_lane_all",
-           "phx_lane_list_all", "phx_lane_all_rl", "phx_lane_all_pk"]
 
 
 def hiprtc_compile(src):
@@ -58,6 +57,31 @@ def lane_source(emu, creator, names, kw, nodes=None):
     return fn(ph._ctx, 2).decode()
 
 
+def lane_kernels(emu):
+    fn = emu.lib.emu_phx_lane_kernels
+    fn.restype = ctypes.c_char_p
+    fn.argtypes = []
+    return fn().decode().split()
+
+
+def elf_symbols(code):
+    """The symbol names of an ELF64 little-endian object (its .symtab and .dynsym)."""
+    assert code[:6] == b"\x7fELF\x02\x01", "not a little-endian ELF64 code object"
+    shoff, = struct.unpack_from("<Q", code, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", code, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", code, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for sh in sections:
+        sh_type, off, size, link, entsize = sh[1], sh[4], sh[5], sh[6], sh[9]
+        if sh_type not in (2, 11):          # SHT_SYMTAB, SHT_DYNSYM
+            continue
+        stroff = sections[link][4]
+        for o in range(off, off + size, entsize):
+            st_name, = struct.unpack_from("<I", code, o)
+            names.add(code[stroff + st_name:code.index(b"\0", stroff + st_name)].decode())
+    return names
+
+
 CASES = {
     "farmer": (farmer.scenario_creator, farmer.scenario_names_creator(200), {"num_scens": 200}, None),
     "aircond": (aircond.scenario_creator, ["scen%d" % i for i in range(27)], {"branching_factors": [3, 3, 3]},
@@ -75,5 +99,8 @@ def test_lane_source_compiles_gfx950(emu, case):
     assert "struct PT" in src, "the lane solver does not serve %s" % case
     rc, log, code = hiprtc_compile(src)
     assert rc == 0, log[-4000:]
-    for k in KERNELS:
-        assert k.encode() in code, k
+    kernels = lane_kernels(emu)
+    assert kernels and len(kernels) == len(set(kernels)), kernels
+    symbols = elf_symbols(code)
+    for k in kernels:
+        assert k in symbols and k + ".kd" in symbols, k
