@@ -292,6 +292,67 @@ int phx_update_w(phx_ctx* ctx, const double* x, const double* xbar_node,
 int phx_expect(phx_ctx* ctx, const double* prob, const double* obj,
                const int32_t* status, double* out, void* stream);
 
+/* Per-(node, slot) primal residuals, local part: for every entry e of the
+ * global node-slot vector
+ *     out[e] = sum over the node's local scenarios s of w(j,s) * |x_N(j,s) - xbar_node[e]|
+ * (j the nonant slot of e; w = wt[j*S+s] when wt_per_slot, else wt[s]), zeros
+ * for nodes absent locally, and out[NNS] = out[0] + ... + out[NNS-1] in index
+ * order.  The caller all-reduces the NNS+1 doubles in place.  Replaces
+ * NormRhoUpdater._compute_primal_residual_norm (extensions/
+ * norm_rho_updater.py:55-96: wt = the scenario probabilities) and
+ * PrimalDualConverger._compute_primal_convergence (convergers/
+ * primal_dual_converger.py:58-85: wt = prob_coeff per slot, the total).
+ * Uses the Compute_Xbar tiles of `tree`; `partial` is a caller-owned buffer of
+ * tree->npart doubles of its own (not the one given to the x-bar reduction).
+ * Fixed summation order: two calls on the same inputs agree bit for bit.    */
+int phx_node_absdev(phx_ctx* ctx, const phx_tree_desc* tree, const double* x,
+                    const double* xbar_node, const double* wt, int32_t wt_per_slot,
+                    double* partial, double* out, void* stream);
+
+/* The norm-rho rule's parameters (norm_rho_updater.py:12-31: the options
+ * convergence_tolerance, rho_increase_multiplier, rho_decrease_multiplier,
+ * primal_dual_difference_factor, rho_converged_decrease_multiplier) and
+ * whether this iteration may decrease (_PHIter >=
+ * iterations_converged_before_decrease, :138).                              */
+typedef struct phx_norm_rho_opts {
+    double  tol;
+    double  rho_increase;
+    double  rho_decrease;
+    double  pd_factor;
+    double  conv_decrease;
+    int32_t allow_decrease;
+} phx_norm_rho_opts;
+
+/* NormRhoUpdater.miditer's update (norm_rho_updater.py:98-104, :122-143) for
+ * every local (node, slot) entry e, given the all-reduced primal residuals:
+ *     dual   = rho_rep * |xbar_node[e] - xbar_prev[e]|     (rho_rep: the slot's
+ *              rho in the node's last local scenario, what the reference's
+ *              dict overwrite leaves on a rank)
+ *     action = 1 if primal > pd_factor*dual and primal > tol           (rho *= rho_increase)
+ *         else 2 if dual > pd_factor*primal and dual > tol, when allow_decrease;
+ *                0 when not                                            (rho /= rho_decrease)
+ *         else 3 if primal < tol and dual < tol                        (rho /= conv_decrease)
+ *         else 0
+ * then xbar_prev[e] = xbar_node[e] (_snapshot_avg, :50-53), and
+ * rho[j][s] scaled by the action of entry xbar_idx[j*S+s] (IEEE
+ * multiplication and division).  action_out [NNS] (int32) and dual_out [NNS]
+ * (may be NULL) read 0 at entries of nodes absent locally.                  */
+int phx_norm_rho(phx_ctx* ctx, const phx_tree_desc* tree, const phx_norm_rho_opts* opts,
+                 const double* primal, const double* xbar_node, double* xbar_prev,
+                 const int32_t* xbar_idx, double* rho, double* dual_out, int32_t* action_out,
+                 void* stream);
+
+/* Local parts of the rho-based stop tests (the caller all-reduces out [2]):
+ *   out[0] = sum_s prob[s] * sum_j rho[j][s]
+ *            (NormRhoConverger._compute_rho_norm, convergers/norm_rho_converger.py:23-29)
+ *   out[1] = sum_s sum_j rho[j][s] * |xbar_node[i] - xbar_prev[i]|, i = xbar_idx[j*S+s]
+ *            (PrimalDualConverger._compute_dual_residual, convergers/
+ *            primal_dual_converger.py:87-110; not probability-weighted);
+ *            0 when xbar_prev is NULL.
+ * Slots in order within a scenario, scenarios in a fixed two-level order.   */
+int phx_rho_sums(phx_ctx* ctx, const double* rho, const double* prob, const double* xbar_node,
+                 const double* xbar_prev, const int32_t* xbar_idx, double* out, void* stream);
+
 /* Scenario-major export of a [N][S] slot array (W or nonant x) into
  * out[S*N + 0..] — the flat layout of PHBase._populate_W_cache /
  * PHHub.send_nonants (phbase.py:346-366, hub.py:562-577).                  */

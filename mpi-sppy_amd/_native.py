@@ -100,11 +100,19 @@ class IterkResult(ctypes.Structure):
     ]
 
 
+class NormRhoOpts(ctypes.Structure):
+    _fields_ = [
+        ("tol", c_double), ("rho_increase", c_double), ("rho_decrease", c_double),
+        ("pd_factor", c_double), ("conv_decrease", c_double), ("allow_decrease", c_int32),
+    ]
+
+
 # every symbol of include/phx.h (tests check the library exports all of them)
 SYMBOLS = [
     "create", "destroy", "last_error", "build_info", "set_problem", "set_bounds", "set_ph_terms",
     "solve", "solve_finish", "objective", "xbar", "update_w", "expect", "export_slots", "last_solve_stats", "jit_info",
     "iterk", "iterk_prepare", "comm_unique_id", "set_comm", "debug_spd_inverse",
+    "node_absdev", "norm_rho", "rho_sums",
 ]
 
 
@@ -159,6 +167,14 @@ class Lib:
         self.comm_unique_id = fn("comm_unique_id", ctypes.c_int, [c_void_p])
         self.set_comm = fn("set_comm", ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32])
         self.debug_spd_inverse = fn("debug_spd_inverse", ctypes.c_int, [c_void_p, c_int32, c_void_p])
+        self.node_absdev = fn("node_absdev", ctypes.c_int,
+                              [c_void_p, ctypes.POINTER(TreeDesc), c_void_p, c_void_p, c_void_p, c_int32,
+                               c_void_p, c_void_p, c_void_p])
+        self.norm_rho = fn("norm_rho", ctypes.c_int,
+                           [c_void_p, ctypes.POINTER(TreeDesc), ctypes.POINTER(NormRhoOpts), c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+        self.rho_sums = fn("rho_sums", ctypes.c_int,
+                           [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 
     def check(self, ctx, rc, what):
         if rc != 0:
