@@ -358,6 +358,53 @@ int phx_rho_sums(phx_ctx* ctx, const double* rho, const double* prob, const doub
  * PHHub.send_nonants (phbase.py:346-366, hub.py:562-577).                  */
 int phx_export_slots(phx_ctx* ctx, const double* src, double* out, void* stream);
 
+/* The nonant values of one donor scenario per tree node, as a node-slot vector:
+ * for every local node v with a local donor (donor_host[v] >= 0, a local
+ * scenario index inside the node's local scenario range) and every slot l of
+ * the node, out[node_off[v] + l] = vals[slot][donor_host[v]]; 0.0 at entries of
+ * nodes whose donor lives on another rank (donor_host[v] = -1) and of nodes
+ * absent locally.  vals is a [N][S] slot array of nonant values (the layout
+ * phx_export_slots reads); donor_host is a HOST array [tree->nnodes], which
+ * must stay unchanged until the call's work has run; out is [NNS].  The
+ * caller all-reduces out by SUM: exactly one rank contributes per node, so the
+ * result is the donor's bits.  Replaces XhatBase._try_one's gather of the
+ * donors' nonant caches and its per-node bcast (extensions/xhatbase.py:73-86
+ * two-stage, :87-123 multistage).  A donor outside its node's local scenarios
+ * is rejected (phx_last_error).  The first call for a tree descriptor reads its
+ * tile ranges back once (they are kept by the descriptor's array addresses).   */
+int phx_donor_gather(phx_ctx* ctx, const phx_tree_desc* tree, const double* vals,
+                     const int32_t* donor_host, double* out, void* stream);
+
+/* Fix every nonant slot j of every local scenario s at
+ * node_vals[xbar_idx[j*S+s]] (lb = ub = value) for the following solves, and,
+ * when x ([n][S]) is given, store the same values into x's nonant columns (a
+ * fixed Var's value is its fixed value, bit for bit).  Replaces
+ * SPOpt._fix_nonants on the values _try_one broadcast (spopt.py:557-591,
+ * extensions/xhatbase.py:208) without a host copy of x or of the bounds.
+ * node_vals = NULL, or phx_set_bounds(ctx, NULL, NULL), restores the problem's
+ * bounds.  Needs no deferred solve pending, as phx_set_bounds.  node_vals and
+ * xbar_idx must stay valid and unchanged while the nonants are fixed.
+ *
+ * With a lane module (phx_jit_info "on"), the first call builds a second one:
+ * the problem's structure with every nonant column fixed and every bound a
+ * per-scenario load, same tuning and kernel list.  While nonants are fixed
+ * through this entry point phx_solve runs that module: its kernels, its
+ * context-owned unscaled [n][S] bound arrays (rows outside the nonants filled
+ * once from the problem's bounds, nonant rows by each call), its own
+ * active-set words and its own solved-before state -- the first fixed solve is
+ * cold, later ones start from the previous candidate's active set, and a solve
+ * after the bounds are restored starts from the PH module's own active set.
+ * The same kernel writes the scaled override arrays of the generic path, so a
+ * lane the module does not certify (an infeasible candidate) falls through to
+ * it as any other lane does.  Fallbacks: a fixed module that does not compile
+ * (its build's register / LDS limits; phx_jit_info reports "fixed-nonant lane
+ * module off: <reason>"; PHX_FIX_LANE=0 asks for that) keeps the generic path,
+ * as do problems served by the workgroup or sparse solvers -- the call is then
+ * only the device-side bound write.  phx_set_bounds with explicit arrays keeps
+ * its meaning and its generic path.                                          */
+int phx_fix_nonants(phx_ctx* ctx, const double* node_vals, const int32_t* xbar_idx,
+                    double* x, void* stream);
+
 int phx_last_solve_stats(const phx_ctx* ctx, phx_solve_stats* out_host);
 
 /* In-place SUM all-reduce of `count` doubles at device `buf` over the ranks,
@@ -467,7 +514,8 @@ int phx_set_comm(phx_ctx* ctx, const void* id_host, int32_t nranks, int32_t rank
 int phx_iterk_prepare(phx_ctx* ctx, const phx_iterk_args* args);
 
 /* Human-readable state of the structure-specialised lane solver for this
- * context ("on: ..." or "off: <reason>").                                   */
+ * context ("on: ..." or "off: <reason>"), and after the first phx_fix_nonants
+ * of its fixed-nonant module ("fixed-nonant lane module on" / "... off: <reason>"). */
 const char* phx_jit_info(const phx_ctx* ctx);
 
 /* Test hook (no reference counterpart): the workgroup solver's Schur

@@ -112,7 +112,7 @@ SYMBOLS = [
     "create", "destroy", "last_error", "build_info", "set_problem", "set_bounds", "set_ph_terms",
     "solve", "solve_finish", "objective", "xbar", "update_w", "expect", "export_slots", "last_solve_stats", "jit_info",
     "iterk", "iterk_prepare", "comm_unique_id", "set_comm", "debug_spd_inverse",
-    "node_absdev", "norm_rho", "rho_sums",
+    "node_absdev", "norm_rho", "rho_sums", "donor_gather", "fix_nonants",
 ]
 
 
@@ -175,6 +175,9 @@ class Lib:
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
         self.rho_sums = fn("rho_sums", ctypes.c_int,
                            [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+        self.donor_gather = fn("donor_gather", ctypes.c_int,
+                               [c_void_p, ctypes.POINTER(TreeDesc), c_void_p, P_i32, c_void_p, c_void_p])
+        self.fix_nonants = fn("fix_nonants", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 
     def check(self, ctx, rc, what):
         if rc != 0:

@@ -91,6 +91,21 @@ inline void set_lane_tuning(LaneStructure& L, double multi_theta, int multi_roun
     L.multi_rounds = on ? (multi_rounds > 0 ? std::min(multi_rounds, 64) : 4) : 0;
 }
 
+// The structure of the same problem with every nonant column fixed at a
+// per-scenario value (phx_fix_nonants): the columns with a slot are marked
+// fixed with both bounds finite, and bnd_vary is on -- PT::bnd_vary() is
+// all-or-nothing, so every column's bounds become run-time loads and the
+// bound literals go.  Tuning, scaling and start scales stay the problem's.
+inline LaneStructure fixed_nonant_structure(const LaneStructure& L) {
+    LaneStructure F = L;
+    for (int j = 0; j < F.n; ++j)
+        if (F.col_slot[j] >= 0) F.fixed[j] = F.lfin[j] = F.ufin[j] = 1;
+    F.bnd_vary = true;
+    F.lb.clear();
+    F.ub.clear();
+    return F;
+}
+
 // Limits for the register-resident kernel (beyond them: generic kernels).
 constexpr int LANE_MAX_N = 64;
 constexpr int LANE_MAX_M = 24;

@@ -510,7 +510,9 @@ class PHBase(SPOpt):
         """The device-driven loop (phx_iterk) runs the same iterations when no
         per-iteration host hook or printout needs the host between steps."""
         o = self.options
-        if self.extensions is not None or self.ph_converger is not None or self.spcomm is not None:
+        if self.ph_converger is not None or self.spcomm is not None:
+            return False
+        if self.extensions is not None and self._ext_hooks_in_loop():
             return False
         if o["display_progress"] or o["verbose"] or o["display_convergence_detail"]:
             return False
@@ -526,6 +528,19 @@ class PHBase(SPOpt):
         if self.NNS == 0 or self.batch.nonant.N == 0:
             return False
         return self._device_loop_solver(self._solve_opts(so))
+
+    _LOOP_HOOKS = ("miditer", "enditer", "enditer_after_sync", "pre_solve_loop", "post_solve_loop",
+                   "pre_solve", "post_solve")
+
+    def _ext_hooks_in_loop(self):
+        """True unless the extension object is an Extension that overrides none of
+        the hooks called inside iterk_loop (XhatSpecific, XhatLooper: they act in
+        post_everything, after the loop, so the iterations may run on the device)."""
+        from .extensions.extension import Extension
+        ext = self.extobject
+        if not isinstance(ext, Extension):
+            return True
+        return any(getattr(type(ext), h, None) is not getattr(Extension, h) for h in self._LOOP_HOOKS)
 
     def _device_loop_solver(self, so):
         """Which solve phx_iterk can run per iteration: the lane solver (jit on),

@@ -134,6 +134,16 @@ class SPBase:
         self.local_scenario_names = self.all_scenario_names[lo:hi]
         leaf = sputils.find_leaves(self.all_nodenames)
         self.nonleaves = [nd for nd in self.all_nodenames if not leaf.get(nd, False)]
+        # the non-leaf nodes as objects (name, stage, kids, scenfirst, scenlast: the
+        # reference's SPBase.nonleaves dict, spbase.py:211, which ScenarioCycler reads)
+        self.nonleaf_nodes = sputils.nonleaf_tree_nodes(self.all_nodenames, S)
+        # {node name: {scenario name: cylinder rank}} from the rank slices
+        # (spbase.py:208; every node's comm here is the cylinder's, so the rank is
+        # the cylinder rank, not a rank within a node's split comm)
+        rank_of = [r for r, (a, b) in enumerate(self._rank_bounds) for _ in range(a, b)]
+        self.scenario_names_to_rank = {
+            nd.name: {self.all_scenario_names[k]: rank_of[k] for k in range(nd.scenfirst, min(nd.scenlast, S - 1) + 1)}
+            for nd in self.nonleaf_nodes.values()}
 
     def _create_scenarios(self, scenario_creator_kwargs):
         if self.scenarios_constructed:

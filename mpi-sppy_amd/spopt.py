@@ -451,6 +451,11 @@ class SPOpt(SPBase):
             self._fixed = np.zeros((S, N), dtype=bool)
             self._fix_val = np.zeros((S, N))
             self._fix_dirty = False
+        if getattr(self, "_fix_val_on_device", False):
+            # fixed on the device (_fix_nonants_device): x's nonant columns hold the
+            # fixed values bit for bit; the host copy is made when first asked for
+            self._fix_val_on_device = False
+            self._fix_val[:] = self._nonant_x()
         return self._fixed, self._fix_val
 
     def _nonant_x(self):
@@ -540,6 +545,7 @@ class SPOpt(SPBase):
         fixed, _ = self._fix_arrays()
         self.nonant_cache = np.ascontiguousarray(self._nonant_x())
         self.fixedness_cache = fixed.copy()
+        self._nonant_cache_dev_stale = True
 
     def _put_nonant_cache(self, cache):
         """Flat scenario-major values into nonant_cache (spopt.py:530-543)."""
@@ -549,6 +555,7 @@ class SPOpt(SPBase):
         S, N = self.nonant_cache.shape
         assert len(cache) >= S * N
         self.nonant_cache[:] = np.asarray(cache[:S * N], dtype=np.float64).reshape(S, N)
+        self._nonant_cache_dev_stale = True
 
     def _restore_nonants(self):
         """Values and fixedness back from nonant_cache / fixedness_cache (spopt.py:638-662)."""
@@ -632,7 +639,8 @@ class SPOpt(SPBase):
         if not getattr(self, "_fix_dirty", False):
             return
         lib = self._native
-        fixed = self._fixed
+        fixed, _ = self._fix_arrays()
+        self._fix_dev = None              # (phx_set_bounds ends a device-side fixing)
         if not fixed.any():
             lib.check(self._ctx, lib.set_bounds(self._ctx, None, None, self._stream()), "set_bounds")
             self._fix_lb = self._fix_ub = None
@@ -652,3 +660,82 @@ class SPOpt(SPBase):
                       "set_bounds")
             self._fix_lb, self._fix_ub = lb, ub
         self._fix_dirty = False
+
+    # ------------------------------------------------------------ device-side fixing
+    # XhatBase._try_one's path: the donors' values are gathered, fixed and (when
+    # asked) restored on the device -- no host copy of x, no [n][S] bound upload.
+    def _nonant_cache_device(self):
+        """``nonant_cache`` as a device [N][S] slot array (the layout
+        phx_export_slots reads), uploaded only after _save_nonants /
+        _put_nonant_cache changed the host cache."""
+        if getattr(self, "nonant_cache", None) is None:
+            raise RuntimeError("Rank {} Scenario {} nonant_cache is None (call _save_nonants first?)"
+                               .format(self.global_rank, self.local_scenario_names[0]))
+        dev = getattr(self, "_nonant_cache_dev", None)
+        if dev is None or getattr(self, "_nonant_cache_dev_stale", True):
+            host = torch.as_tensor(np.ascontiguousarray(self.nonant_cache.T), dtype=torch.float64)
+            if dev is None:
+                dev = self._nonant_cache_dev = host.to(self.device).contiguous()
+            else:
+                dev.copy_(host)
+            self._nonant_cache_dev_stale = False
+        return dev
+
+    def _donor_values(self, donor):
+        """[NNS] device vector of each tree node's donor values (phx_donor_gather
+        on the nonant cache, then one SUM all-reduce: exactly one rank
+        contributes per node).  ``donor``: int32 [local nodes], the donor's local
+        scenario index or -1 when it lives on another rank."""
+        lib = self._native
+        if getattr(self, "_donor_out", None) is None:
+            self._donor_out = torch.zeros(max(self.NNS, 1), dtype=torch.float64, device=self.device)
+        self._donor_host = np.ascontiguousarray(donor, dtype=np.int32)     # (kept until the next call)
+        lib.check(self._ctx, lib.donor_gather(self._ctx, ctypes.byref(self._tree),
+                                              self._nonant_cache_device().data_ptr(),
+                                              self._donor_host.ctypes.data_as(_native.P_i32),
+                                              self._donor_out.data_ptr(), self._stream()), "donor_gather")
+        if self.n_proc > 1:
+            self.mpicomm.allreduce_(self._donor_out)
+        return self._donor_out
+
+    def _fix_nonants_device(self, node_vals):
+        """Fix every local nonant at ``node_vals[xbar_idx]`` (a device [NNS]
+        vector, kept alive here while fixed) and give x those values:
+        phx_fix_nonants.  The host fixedness is all True; the host values are
+        read back from x only if something asks for them (_fix_arrays)."""
+        if self._bundles is not None:
+            raise NotImplementedError("fixing nonants of bundled scenarios (bundles_per_rank) is not supported")
+        self._settle()
+        lib = self._native
+        if getattr(self, "_fixed", None) is None:
+            self._fix_arrays()
+        lib.check(self._ctx, lib.fix_nonants(self._ctx, node_vals.data_ptr(), self._xbar_idx_t.data_ptr(),
+                                             self._x.data_ptr(), self._stream()), "fix_nonants")
+        self._fix_dev = node_vals
+        self._fixed[:] = True             # (not through _fix_arrays: no read-back of the previous candidate)
+        self._fix_val_on_device = True
+        self._fix_dirty = False
+        self._fix_lb = self._fix_ub = None
+        self._x_touched = True
+        self._conv_cache = None
+        self._bump()
+
+    def _restore_nonants_device(self):
+        """_restore_nonants when the nonants were fixed by _fix_nonants_device and
+        the cached fixedness is all False (the usual case): the problem's bounds
+        back (phx_fix_nonants(NULL): the PH lane module and its own active
+        sets again) and x's nonant columns from the device copy of the cache."""
+        if getattr(self, "_fix_dev", None) is None or self.fixedness_cache.any():
+            return self._restore_nonants()
+        self._settle()
+        lib = self._native
+        lib.check(self._ctx, lib.fix_nonants(self._ctx, None, None, None, self._stream()), "fix_nonants")
+        self._fix_dev = None
+        self._fixed[:] = False
+        self._fix_val_on_device = False
+        self._fix_val[:] = self.nonant_cache
+        self._fix_dirty = False
+        self._fix_lb = self._fix_ub = None
+        self._x.view(-1, self._S).index_copy_(0, self._slot_cols_dev, self._nonant_cache_device())
+        self._conv_cache = None
+        self._bump()

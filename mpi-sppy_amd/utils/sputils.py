@@ -73,6 +73,61 @@ def attach_root_node(model, firstobj, varlist, nonant_ef_suppl_list=None):
     ]
 
 
+class TreeNode:
+    """A scenario-tree node as the reference's ``_TreeNode`` exposes it
+    (sputils.py:675-724): ``name``, ``stage`` (1-based), ``kids``, ``is_leaf``
+    and the indices ``scenfirst`` .. ``scenlast`` (inclusive) of its scenarios
+    in ``all_scenario_names``."""
+
+    def __init__(self, name, stage, scenfirst, scenlast, is_leaf=False):
+        self.name = name
+        self.stage = stage
+        self.scenfirst = scenfirst
+        self.scenlast = scenlast
+        self.is_leaf = is_leaf
+        self.kids = []
+
+    def __repr__(self):
+        return "TreeNode(%s, scenarios %d..%d)" % (self.name, self.scenfirst, self.scenlast)
+
+
+def nonleaf_tree_nodes(all_nodenames, scen_count):
+    """{name: TreeNode} of the non-leaf nodes, ROOT first and depth first as
+    the reference's ``_ScenTree.nonleaves`` (sputils.py:755-763).  Scenarios are
+    the leaves in depth-first order (children by their number), one per leaf;
+    a two-stage tree (``["ROOT"]``) has no leaf nodes and ROOT owns every
+    scenario."""
+    if all_nodenames is None or list(all_nodenames) == ["ROOT"]:
+        return {"ROOT": TreeNode("ROOT", 1, 0, scen_count - 1)}
+    names = set(all_nodenames)
+    out = {}
+
+    def make(name, stage, first):
+        k = 0
+        kids = []
+        nxt = first
+        while "%s_%d" % (name, k) in names:
+            kid = make("%s_%d" % (name, k), stage + 1, nxt)
+            nxt = kid.scenlast + 1
+            kids.append(kid)
+            k += 1
+        if not kids:
+            return TreeNode(name, stage, first, first, is_leaf=True)
+        node = TreeNode(name, stage, first, nxt - 1)
+        node.kids = kids
+        return node
+
+    def collect(node):
+        if node.is_leaf:
+            return
+        out[node.name] = node
+        for kid in node.kids:
+            collect(kid)
+
+    collect(make("ROOT", 1, 0))
+    return out
+
+
 def find_leaves(all_nodenames):
     if all_nodenames is None or all_nodenames == ["ROOT"]:
         return {"ROOT": False}
