@@ -174,11 +174,12 @@ def prepare(ev, o):
     ev._restore_nonants()
 
 
-def check_try_one(ev, model, size, donor_dicts, lane=False, sample=None):
+def check_try_one(ev, model, size, donor_dicts, lane=False, sample=None, scens=None):
     """_try_one for each donor dict in turn (restore_nonants False, True, False,
     ...) against oracle.ph.evaluate_xhat; with ``lane`` every solve must be
-    certified by the lane solver alone."""
-    scens = oracle_scens(model, size)
+    certified by the lane solver alone.  scens: the oracle's scenarios of a
+    model other than farmer / aircond."""
+    scens = scens if scens is not None else oracle_scens(model, size)
     o = oph.OraclePH(scens, rho=1.0)
     o.iter0()
     prepare(ev, o)
