@@ -134,11 +134,14 @@ def _pattern(rng, n, m, ckind, rkind, empty, arrow, nnz):
 
 class SynthFamily:
     """One family at one seed: ``creator`` / ``names`` / ``kwargs`` / ``nodenames`` for
-    the engine, ``scens()`` for the oracle, ``flags`` the features realised."""
+    the engine, ``scens()`` for the oracle, ``flags`` the features realised.  ``prob`` /
+    ``node_prob``: optional scenario probabilities and conditional probabilities of the
+    stage-2 nodes (weight_cases.py); they reach the creator, the batch creator and
+    ``scen()`` and nothing else (the numbers drawn do not depend on them)."""
 
     DRAWS = 32
 
-    def __init__(self, family, seed, n=None, m=None, N=None, S=70):
+    def __init__(self, family, seed, n=None, m=None, N=None, S=70, prob=None, node_prob=None):
         # PH has work to do only where the scenarios disagree on a nonant.  Nothing in
         # the construction forces that (every nonant may sit at a shared bound), so
         # the numbers are drawn again, from the next stream of the same seed, until
@@ -152,6 +155,31 @@ class SynthFamily:
         else:
             raise RuntimeError("synth family %s seed %d: no draw on which the scenarios disagree" % (family, seed))
         self.flags["draw"] = draw
+        if prob is not None or node_prob is not None:
+            self._set_weights(prob, node_prob)
+
+    def _set_weights(self, prob, node_prob):
+        """Scenario probabilities (S,) and, on a three-stage tree, the conditional
+        probabilities (bf[0],) of the stage-2 nodes; None: 1 / S and 1 / bf[0], by the
+        expressions a family without weights has always used."""
+        self.prob = None if prob is None else np.asarray(prob, dtype=np.float64).copy()
+        self.node_prob = None if node_prob is None else np.asarray(node_prob, dtype=np.float64).copy()
+        assert self.prob is None or self.prob.shape == (self.S,)
+        assert self.node_prob is None or (self.bf and self.node_prob.shape == (self.bf[0],))
+        self.creator = self._make_creator()
+
+    def weighted(self, prob=None, node_prob=None):
+        """The same scenarios (shared arrays, no new draw) under other probabilities."""
+        import copy
+        fam = copy.copy(self)
+        fam._set_weights(prob, node_prob)
+        return fam
+
+    def scen_prob(self, k):
+        return 1.0 / self.S if self.prob is None else float(self.prob[k])
+
+    def node_cond_prob(self, v):
+        return 1.0 / self.bf[0] if self.node_prob is None else float(self.node_prob[v])
 
     def _nonants_disagree(self, count=8, tol=1e-2):
         from scipy.optimize import linprog
@@ -178,6 +206,7 @@ class SynthFamily:
         m = self.m = m or sp["m"]
         N = N or sp["N"]
         self.S = S
+        self.prob = self.node_prob = None
         self.stage_N = tuple(N) if isinstance(N, (tuple, list)) else (N,)
         self.N = sum(self.stage_N)
         self.bf = sp.get("bf")
@@ -349,11 +378,12 @@ class SynthFamily:
                 sputils.attach_root_node(m, first, [v[j] for j in cols[0]])
             else:
                 second = lm.LinExpr({j: fam.c[k, j] for j in cols[1]}, 0.0, m)
+                node = k // fam.bf[1]
                 m._mpisppy_node_list = [
                     ScenarioNode("ROOT", 1.0, 1, first, [v[j] for j in cols[0]], m),
-                    ScenarioNode("ROOT_%d" % (k // fam.bf[1]), 1.0 / fam.bf[0], 2, second, [v[j] for j in cols[1]], m,
+                    ScenarioNode("ROOT_%d" % node, fam.node_cond_prob(node), 2, second, [v[j] for j in cols[1]], m,
                                  parent_name="ROOT")]
-            m._mpisppy_probability = 1.0 / fam.S
+            m._mpisppy_probability = fam.scen_prob(k)
             return m
         return scenario_creator
 
@@ -369,7 +399,7 @@ class SynthFamily:
             spec = NonantSpec(list(range(fam.N)), [1] * fam.N, list(range(fam.N)), [None], [np.ones(len(ks))],
                               fam.var_names[:fam.N])
             return BatchData(names, fam.rowptr, fam.colidx, fam.A[ks], fam.bl[ks], fam.bu[ks], fam.lb[ks],
-                             fam.ub[ks], fam.c[ks], fam.c0, lm.minimize, [1.0 / fam.S] * len(ks), spec,
+                             fam.ub[ks], fam.c[ks], fam.c0, lm.minimize, [fam.scen_prob(k) for k in ks], spec,
                              list(fam.var_names))
         creator.batch_creator = batch_creator
         return creator
@@ -384,9 +414,9 @@ class SynthFamily:
         cols = self._node_cols()
         nodes = [("ROOT", 1.0, 1, cols[0])]
         if self.bf:
-            nodes.append(("ROOT_%d" % (k // self.bf[1]), 1.0 / self.bf[0], 2, cols[1]))
+            nodes.append(("ROOT_%d" % (k // self.bf[1]), self.node_cond_prob(k // self.bf[1]), 2, cols[1]))
         return om.Scen(self.names[k], self.var_names, self.c[k], self.c0, self.dense_A(k), self.bl[k], self.bu[k],
-                       self.lb[k], self.ub[k], nodes, 1.0 / self.S)
+                       self.lb[k], self.ub[k], nodes, self.scen_prob(k))
 
     def scens(self, ks=None):
         return [self.scen(k) for k in (range(self.S) if ks is None else ks)]

@@ -23,6 +23,12 @@ one-block phx_xbar must return zeros for the absent ones, and farmer on
 2 x 1,000 scenarios (the one-block kernel's modes 1 and 2 under a real
 all-reduce).
 
+Two more run a synthetic two-stage family under non-uniform probabilities and a
+per-(scenario, slot) rho from a rho_setter (weight_cases.py) at S = 70 on 2
+ranks, fused and unfused: each rank's rho_setter writes its own slice, and each
+rank's pc-weighted partials are sums under probabilities that add up to one
+over both ranks only.
+
 Each multi-rank run is checked against the one-process run of the same
 scenarios (conv_ranks = world size: the reference's per-rank normalisation,
 sputils.py:803-810 slices).  Tolerances: the ranks' x-bar sums add in another
@@ -53,6 +59,12 @@ CASES = {
     # every phx_xbar call (the buffer is all-reduced in place)
     "aircond3-host": ("aircond", 3, [5, 2, 2], 20, 1e-3, 0, None, 0),
     "farmer-host": ("farmer", 2, 2000, 60, 1.0, 0, None, 0),
+    # a synthetic two-stage family under non-uniform probabilities and a per-slot rho
+    # from a rho_setter (weight_cases.py), S = 70: each rank's fused kernel forms
+    # pc-weighted partials of a tree whose probabilities sum to one over both ranks
+    # only (a rank that normalised by its own mass would double x-bar)
+    "weighted-fused": ("weighted", 2, 70, 4, 1e-10, 1, None, 1),
+    "weighted-unfused": ("weighted", 2, 70, 4, 1e-10, 0, None, 1),
 }
 
 
@@ -73,7 +85,11 @@ def _run_case(case, lib, device, mpicomm=None, conv_ranks=None):
     opts = {"convthresh": thresh, "iter0_solver_options": dict(so or {}), "iterk_solver_options": iterk}
     if conv_ranks:
         opts["conv_ranks"] = conv_ranks
-    if model == "farmer":
+    if model == "weighted":
+        import weight_cases as wc
+        ph, conv, Eobj, tb = wc.run(lib, device, wc.case("vary_all", "p_rho", S=size), iters, mpicomm=mpicomm,
+                                    options=opts)
+    elif model == "farmer":
         ph, conv, Eobj, tb = run_engine(farmer.scenario_creator, farmer.scenario_names_creator(size),
                                         {"num_scens": size}, iters, lib=lib, device=device, mpicomm=mpicomm,
                                         options=opts)
@@ -134,7 +150,7 @@ def test_ranks_match_one_gpu(gpu_lib, case):
         # the multi-rank path ran on the device: fused where asked (two-stage, one
         # segment per rank), the same iteration count and stop as one process
         if loop:
-            assert st["fused"] == bool(fused and model == "farmer"), st
+            assert st["fused"] == bool(fused and model in ("farmer", "weighted")), st
         else:
             assert "fused" not in st, st
         assert r["iters"] == one["iters"] and st["converged"] == one["stats"]["converged"], (st, one["stats"])

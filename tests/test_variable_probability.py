@@ -1,7 +1,9 @@
 """variable_probability (spbase.py:394-452, phbase.py:27-107 and 314-318): per
 (scenario, nonant) probabilities replace prob_coeff in x-bar, zero-probability
 nonants keep W = 0, and the sums per node and variable must be one.  Checked
-against the oracle with the same per-slot probabilities (CPU, emulation)."""
+against the oracle with the same per-slot probabilities (CPU, emulation).  The
+S = 70 synthetic case, on the emulation and on the kernels, is in
+test_weights.py / test_weights_gpu.py (weight_cases.check_variable_probability)."""
 import numpy as np
 import pytest
 
