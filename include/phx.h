@@ -405,6 +405,65 @@ int phx_donor_gather(phx_ctx* ctx, const phx_tree_desc* tree, const double* vals
 int phx_fix_nonants(phx_ctx* ctx, const double* node_vals, const int32_t* xbar_idx,
                     double* x, void* stream);
 
+/* One Fixer decision pass over the global node-slot vector, a thread per entry
+ * e < NNS.  Replaces Fixer._update_fix_counts and the decisions of Fixer.iterk
+ * (extensions/fixer.py:114-129, 226-304; iter0 = 0) or those of Fixer.iter0
+ * (:131-223; iter0 = 1) with no host loop over scenarios and nonants.
+ * xbar_node / xsqbar_node are the all-reduced [NNS] averages.  Per-entry
+ * tables, all [NNS]: th (the threshold on sqrt|xbar^2 - xsqbar|), nb / lbk /
+ * ubk (the lags; -1 is the reference's None), ent_lb / ent_ub (the column's
+ * bounds; +-inf allowed).  In/out, all [NNS]: count (iterations converged in a
+ * row), fixed (0 free, 1 fixed by nb, 2 at lb, 3 at ub) and fix_val.
+ *     diff = xb*xb - xsq (each operation rounded once);
+ *     converged iff -diff < th*th and diff < th*th.
+ * iterk rule: an entry already fixed is skipped (count untouched); count += 1
+ * if converged, else count = 0; then with fx = count > 0:
+ *     nb >= 0 and nb <= fx                           fixed = 1 at xb
+ *     else lbk >= 0, lbk < fx, xb - lb < boundtol    fixed = 2 at lb
+ *     else ubk >= 0, ubk < fx, ub - xb < boundtol    fixed = 3 at ub
+ * iter0 rule (count unused): converged and nb >= 0 fixes at xb; else lbk >= 0
+ * and xb - lb < boundtol at lb; else ubk >= 0 and ub - xb < boundtol at ub.
+ * Entries of nodes absent on this rank take the same decisions: the inputs
+ * are identical on every rank, so no collective is needed.  The number of
+ * entries this call fixed is counted in a device word of the context and,
+ * when nfixed_host (pinned host memory) is given, copied there on the stream:
+ * valid once the stream's work up to here has run.                          */
+int phx_fixer_step(phx_ctx* ctx, int32_t NNS, const double* xbar_node, const double* xsqbar_node,
+                   const double* th, const int32_t* nb, const int32_t* lbk, const int32_t* ubk,
+                   const double* ent_lb, const double* ent_ub, double boundtol, int32_t iter0,
+                   int32_t* count, int32_t* fixed, double* fix_val, int32_t* nfixed_host, void* stream);
+
+/* The partial form of phx_fix_nonants: slot j of local scenario s, with
+ * e = xbar_idx[j*S+s], is fixed at node_vals[e] where node_fixed[e] != 0
+ * (lb = ub = value, and the value stored into x when x is given); elsewhere
+ * the column keeps the problem's own bounds and x is untouched.  Replaces
+ * xvar.fix(...) plus the persistent solver's update_var of Fixer.iter0 /
+ * Fixer.iterk (extensions/fixer.py:176-194, 264-284) without a host mask or an
+ * [n][S] bound upload.  node_vals, node_fixed and xbar_idx must stay valid
+ * while the fixing is on (their contents may grow: call again after a change).
+ * node_vals = NULL, or phx_set_bounds(ctx, NULL, NULL), restores the problem's
+ * bounds and the PH lane module; phx_iterk refuses to run while fixed.
+ *
+ * slot_fixed_host: HOST uint8 [N], 1 where slot j is fixed in EVERY local
+ * scenario; NULL when the fixed set differs between local scenarios (tree
+ * nodes that fixed different slots).  With it, and with a lane module, the
+ * library builds a fixed-subset lane module: the PH module's structure with
+ * the masked nonant columns fixed and every bound a per-scenario load (same
+ * tuning, waves, defines and kernel list; with every slot masked its source is
+ * the fixed-nonant module's).  One subset module is kept; a changed mask
+ * replaces it (the compile is cached by source text).  It shares the
+ * fixed-nonant module's unscaled bound arrays and has its own active-set
+ * words: the first solve on a new subset module is cold, later ones start
+ * from the previous solve's active set, and after the bounds are restored the
+ * PH module continues from its own.  With NULL, without a lane module, when
+ * the module does not compile, or with PHX_FIX_LANE=0, the call is only the
+ * bound write and solves take the generic path (which stores the fixed values
+ * into x's fixed columns again); phx_jit_info reports "fixed-subset lane
+ * module on (k of N slots)" or "fixed-subset lane module off: <reason>".    */
+int phx_fix_nonants_where(phx_ctx* ctx, const double* node_vals, const int32_t* node_fixed,
+                          const int32_t* xbar_idx, const uint8_t* slot_fixed_host, double* x,
+                          void* stream);
+
 int phx_last_solve_stats(const phx_ctx* ctx, phx_solve_stats* out_host);
 
 /* In-place SUM all-reduce of `count` doubles at device `buf` over the ranks,
@@ -515,7 +574,9 @@ int phx_iterk_prepare(phx_ctx* ctx, const phx_iterk_args* args);
 
 /* Human-readable state of the structure-specialised lane solver for this
  * context ("on: ..." or "off: <reason>"), and after the first phx_fix_nonants
- * of its fixed-nonant module ("fixed-nonant lane module on" / "... off: <reason>"). */
+ * of its fixed-nonant module ("fixed-nonant lane module on" / "... off: <reason>"),
+ * and after a phx_fix_nonants_where of the current fixed-subset module
+ * ("fixed-subset lane module on (k of N slots)" / "... off: <reason>").      */
 const char* phx_jit_info(const phx_ctx* ctx);
 
 /* Test hook (no reference counterpart): the workgroup solver's Schur

@@ -113,6 +113,7 @@ SYMBOLS = [
     "solve", "solve_finish", "objective", "xbar", "update_w", "expect", "export_slots", "last_solve_stats", "jit_info",
     "iterk", "iterk_prepare", "comm_unique_id", "set_comm", "debug_spd_inverse",
     "node_absdev", "norm_rho", "rho_sums", "donor_gather", "fix_nonants",
+    "fixer_step", "fix_nonants_where",
 ]
 
 
@@ -178,6 +179,11 @@ class Lib:
         self.donor_gather = fn("donor_gather", ctypes.c_int,
                                [c_void_p, ctypes.POINTER(TreeDesc), c_void_p, P_i32, c_void_p, c_void_p])
         self.fix_nonants = fn("fix_nonants", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+        self.fixer_step = fn("fixer_step", ctypes.c_int,
+                             [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+        self.fix_nonants_where = fn("fix_nonants_where", ctypes.c_int,
+                                    [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 
     def check(self, ctx, rc, what):
         if rc != 0:

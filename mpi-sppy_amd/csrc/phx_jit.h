@@ -96,10 +96,13 @@ inline void set_lane_tuning(LaneStructure& L, double multi_theta, int multi_roun
 // fixed with both bounds finite, and bnd_vary is on -- PT::bnd_vary() is
 // all-or-nothing, so every column's bounds become run-time loads and the
 // bound literals go.  Tuning, scaling and start scales stay the problem's.
-inline LaneStructure fixed_nonant_structure(const LaneStructure& L) {
+// slot_mask ([nslot], null: every slot) picks the nonant columns to fix
+// (phx_fix_nonants_where: the slots fixed in every scenario); the others keep
+// the problem's flags.
+inline LaneStructure fixed_nonant_structure(const LaneStructure& L, const uint8_t* slot_mask = nullptr) {
     LaneStructure F = L;
     for (int j = 0; j < F.n; ++j)
-        if (F.col_slot[j] >= 0) F.fixed[j] = F.lfin[j] = F.ufin[j] = 1;
+        if (F.col_slot[j] >= 0 && (!slot_mask || slot_mask[F.col_slot[j]])) F.fixed[j] = F.lfin[j] = F.ufin[j] = 1;
     F.bnd_vary = true;
     F.lb.clear();
     F.ub.clear();

@@ -154,5 +154,22 @@ def scenario_names_creator(num_scens, start=None):
     return ["Scenario%d" % i for i in range(start, start + num_scens)]
 
 
+def id_fix_list_fct(s):
+    """The tuples the Fixer uses (sslp.py:41-65): no iter0 list, and for the
+    general iterations th=0, nb=None, lb=20, ub=20 on the first-stage facility
+    variables.  ``s`` is the scenario's model, or its view when the scenarios
+    come from ``batch_creator`` (the ROOT nonants are the facility variables).
+    As in the reference this is an illustration: the runs are not long enough
+    to fix anything.  sslp is served by the workgroup solver, so a solve after
+    a fix would take the generic path (there is no fixed-subset build of it)."""
+    from ..extensions import fixer
+    if hasattr(s, "FacilityOpen"):
+        xvars = [s.FacilityOpen[i] for i in s.FacilityOpen]
+    else:
+        xvars = list(s._mpisppy_data.nonant_indices.values())
+    iterktuples = [fixer.Fixer_tuple(v, th=0, nb=None, lb=20, ub=20) for v in xvars]
+    return None, iterktuples
+
+
 def scenario_denouement(rank, scenario_name, scenario):
     pass

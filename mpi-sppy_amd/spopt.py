@@ -720,6 +720,40 @@ class SPOpt(SPBase):
         self._conv_cache = None
         self._bump()
 
+    def _fix_where_device(self, node_fixed, node_vals, host=None):
+        """Fix local slot j of scenario s at ``node_vals[e]`` where
+        ``node_fixed[e] != 0`` (e = xbar_idx[j, s]; device [NNS] int32 / float64
+        vectors, kept alive here while fixed) and leave the other nonants on the
+        problem's bounds: phx_fix_nonants_where (the Fixer's path).  The host
+        fixedness and values are updated from one read-back of the two vectors,
+        so ``xvar.is_fixed()`` and the save / restore family stay right; when
+        every local scenario fixes the same slots the library solves on its
+        fixed-subset lane module."""
+        if self._bundles is not None:
+            raise NotImplementedError("fixing nonants of bundled scenarios (bundles_per_rank) is not supported")
+        self._settle()
+        lib = self._native
+        fixed, fv = self._fix_arrays()
+        # (host: the caller's host copies of the two vectors, when it has them)
+        how, vals = host if host is not None else (node_fixed.cpu().numpy(), node_vals.cpu().numpy())
+        idx = self._xbar_idx                               # [N][S] entries
+        m = (how[idx] != 0).T                              # [S][N]
+        fixed[:] = m
+        fv[m] = np.ascontiguousarray(vals[idx].T)[m]
+        every = m.all(axis=0) if m.shape[0] else np.zeros(m.shape[1], dtype=bool)
+        uniform = bool((m == every[None, :]).all())
+        self._slot_fixed_host = np.ascontiguousarray(every, dtype=np.uint8)      # (kept until the next call)
+        lib.check(self._ctx, lib.fix_nonants_where(
+            self._ctx, node_vals.data_ptr(), node_fixed.data_ptr(), self._xbar_idx_t.data_ptr(),
+            self._slot_fixed_host.ctypes.data if uniform else None, self._x.data_ptr(), self._stream()),
+            "fix_nonants_where")
+        self._fix_dev = (node_vals, node_fixed)
+        self._fix_dirty = False
+        self._fix_lb = self._fix_ub = None
+        self._x_touched = True
+        self._conv_cache = None
+        self._bump()
+
     def _restore_nonants_device(self):
         """_restore_nonants when the nonants were fixed by _fix_nonants_device and
         the cached fixedness is all False (the usual case): the problem's bounds

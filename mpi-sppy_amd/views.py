@@ -104,6 +104,12 @@ class _VarView:
         return int(list(self._opt.batch.nonant.slot_col).index(self._col))
 
     @property
+    def varid(self):
+        """What identifies this nonant in rho_setter-style lists when there is
+        no per-scenario model to take ``id(var)`` from."""
+        return ("nonant", self._slot())
+
+    @property
     def value(self):
         return float(self._opt._host("x")[self._col, self._s])
 
@@ -162,6 +168,31 @@ class _VarView:
         return False
 
 
+class _VaridIndex:
+    """``varid_to_nonant_index`` of one scenario: looked up, never enumerated
+    (the ids of model variables are known only to the models)."""
+
+    def __init__(self, view):
+        self._view = view
+
+    def __getitem__(self, vid):
+        v = self._view
+        if isinstance(vid, tuple) and len(vid) == 2 and vid[0] == "nonant":
+            j = int(vid[1])
+            if not 0 <= j < len(v._keys()):
+                raise KeyError(vid)
+        else:
+            j = v._slot_of_varid(vid)
+        return v._keys()[j]
+
+    def __contains__(self, vid):
+        try:
+            self[vid]
+            return True
+        except (KeyError, ValueError):
+            return False
+
+
 class _ModelNS:
     def __init__(self, view):
         opt = view._opt
@@ -184,6 +215,14 @@ class _DataNS:
         nn = opt.batch.nonant
         return {k: _VarView(opt, v._s, int(nn.slot_col[j]), nn.var_names[j])
                 for j, k in enumerate(v._keys())}
+
+    @property
+    def varid_to_nonant_index(self):
+        """{variable id: (ndn, i)} (spbase.py:_attach_varid_to_nonant_index).
+        The id is what rho_setter lists carry: ``id(var)`` of a variable of this
+        scenario's model (needs per-scenario models), or ``var.varid`` of a
+        nonant view from ``nonant_indices`` (works without them)."""
+        return _VaridIndex(self._view)
 
     @property
     def nlens(self):
