@@ -243,6 +243,15 @@ int phx_set_ph_terms(phx_ctx* ctx, const double* W, const double* rho,
  * incl. PH terms, = outer bound), status_out[S] (1 optimal, 2 iteration limit,
  * 3 numerical failure, 4 infeasible: a Farkas certificate from the interior
  * point), iters_out[S].  *total_iters_host = iterations run.
+ * Row duals: y_out holds the multipliers of the Lagrangian
+ *      L(x, y) = f(x) - y'(A x),   f(x) = c'x + qN'x_N + 0.5 pN' x_N^2,
+ * of the minimisation form the library was given (the caller negates a
+ * maximisation before phx_set_problem), in unscaled quantities, whichever tier
+ * solved the lane: y_i >= 0 on a row active at its lower side bl, y_i <= 0 on
+ * a row active at its upper side bu, y_i = 0 on an inactive row, either sign
+ * on an equality row.  The reduced costs z = grad f(x) - A'y are >= 0 on a
+ * column at lb, <= 0 at ub and 0 strictly between (a fixed column: any).
+ * phx_iterk writes the same convention through args->y.
  * Synchronises with the host once per check_every iterations.              */
 int phx_solve(phx_ctx* ctx, const phx_solve_opts* opts,
               double* x_out, double* y_out, double* obj_out,

@@ -7,7 +7,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import all_certified, oracle_continue_from, ph_options, REF_W, REF_XBAR, rel, run_engine
+from helpers import (all_certified, kkt_recheck, oracle_continue_from, ph_options, REF_W, REF_XBAR, rel,
+                     run_engine)
 from mpisppy_amd.opt.ph import PH
 from mpisppy_amd.examples import aircond, farmer
 from mpisppy_amd.utils import sputils
@@ -42,6 +43,7 @@ def test_farmer30_modes_vs_oracle(emu, oracle_farmer30, mode):
     assert rel(Eobj, oE) < 1e-9
     assert rel(conv, oc) < 1e-8
     assert all(s["not_optimal"] == 0 for s in ph.solve_stats)
+    kkt_recheck(ph, tag="farmer S=30 %s" % (mode,))
 
 
 def test_per_scenario_models_equal_batch(emu):
@@ -68,6 +70,7 @@ def test_aircond_multistage_emu(emu):
     xb = ph.xbar_by_node()
     assert len(xb) == 13
     assert rel(xb["ROOT"][0], o.xbar[0, 0:2]) < 1e-12
+    kkt_recheck(ph, tag="aircond 3x3x2")
 
 
 MULTI_SETTING = (0.2, 4)      # bench.py's C4 solver options (test_bench_settings pins them)
@@ -116,7 +119,7 @@ def test_aircond_all_builds_bit_equal_gpu(gpu_lib, monkeypatch):
     """The small-batch whole-solve kernel's three builds (phx_lane_all: the
     register build; _rl: its data re-loaded per round; _pk: parked in LDS, the
     default where the register build spills) run the same per-lane arithmetic
-    on the same values: x, W, x-bar and conv bit for bit equal on configs[3]
+    on the same values: x, y, W, x-bar and conv bit for bit equal on configs[3]
     with the bench's C4 setting, and each build is the one that ran."""
     bfs = [10, 10, 10]
     names = ["scen%d" % i for i in range(int(np.prod(bfs)))]
@@ -131,7 +134,8 @@ def test_aircond_all_builds_bit_equal_gpu(gpu_lib, monkeypatch):
         info = ph._native.jit_info(ph._ctx).decode()
         assert (tag in info) if tag else ("all=" not in info), info
         assert all_certified(ph)
-        out[build] = (ph._host("x"), ph.W_array(), conv, Eobj)
+        kkt_recheck(ph, tag="aircond 10x10x10, build %s" % build)
+        out[build] = (ph._host("x"), ph._y.cpu().numpy(), ph.W_array(), conv, Eobj)
     for build in ("reload", "park"):
         for a, b in zip(out["reg"], out[build]):
             assert np.array_equal(np.asarray(a), np.asarray(b)), build
@@ -305,6 +309,8 @@ def test_farmer_cm10_workgroup_warm_pass(emu):
     assert all(r["not_optimal"] == 0 for r in ph1.solve_stats)
     assert rel(ph1.xbar_by_node()["ROOT"][0], ph0.xbar_by_node()["ROOT"][0]) < 1e-9
     assert rel(ph1.W_array(), ph0.W_array()) < 1e-8
+    kkt_recheck(ph1, tag="farmer cm=10, workgroup pass")
+    kkt_recheck(ph0, tag="farmer cm=10, wg_warm 0")
     # Iter0 LPs are degenerate at crops_multiplier=10 (equal optimum, different
     # vertices), so check as test_sslp does: trivial bound, then the last
     # iteration's subproblems re-solved by the oracle from the engine's own W /

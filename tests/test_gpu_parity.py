@@ -9,7 +9,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import all_certified, oracle_continue_from, ph_options, REF_W, REF_XBAR, rel, run_engine
+from helpers import (all_certified, kkt_recheck, oracle_continue_from, ph_options, REF_W, REF_XBAR, rel,
+                     run_engine)
 from mpisppy_amd.examples import farmer, aircond
 from mpisppy_amd.opt.ph import PH
 from oracle import models as om, ph as oph
@@ -43,6 +44,7 @@ def test_farmer_many_vs_oracle(gpu_lib, S):
     assert rel(ph.W_array(), o.W) < 1e-7
     assert rel(Eobj, oE) < 1e-8
     assert all_certified(ph)
+    kkt_recheck(ph, tag="farmer S=%d, fused loop" % S)
 
 
 def test_aircond_multistage_vs_oracle(gpu_lib):
@@ -58,6 +60,7 @@ def test_aircond_multistage_vs_oracle(gpu_lib):
     assert rel(tb, otb) < 1e-9
     assert rel(Eobj, oE) < 1e-8
     assert rel(ph.W_array(), o.W) < 1e-7
+    kkt_recheck(ph, tag="aircond 3x3x2")
 
 
 def test_lane_and_generic_paths_agree(gpu_lib):
@@ -213,6 +216,9 @@ def test_native_loop_straggler_stops_gpu(gpu_lib, so, fused):
     from test_engine_emu import check_native_vs_host
     a, b = check_native_vs_host(gpu_lib, None, "farmer", S=2000, solver=so, fused=fused)
     assert a.iterk_stats["straggler_stops"] > 0
+    # y of the lanes another tier finished after a stop, and the host loop's
+    kkt_recheck(a, tag="farmer stragglers %s fused=%d, device loop" % (so, fused))
+    kkt_recheck(b, tag="farmer stragglers %s, host loop" % (so,))
 
 
 def test_affine_map_path_matches_oracle_gpu(gpu_lib, monkeypatch):
@@ -293,6 +299,8 @@ def test_farmer_cm10_1000_workgroup_gpu(gpu_lib):
     assert rel(ph1.xbar_by_node()["ROOT"][0], ph0.xbar_by_node()["ROOT"][0]) < 1e-8
     assert rel(ph1.W_array(), ph0.W_array()) < 1e-6
     assert rel(res[1][2], res[0][2]) < 1e-9
+    kkt_recheck(ph1, tag="farmer cm=10, workgroup pass")
+    kkt_recheck(ph0, tag="farmer cm=10, wg_warm 0")
     W, xb, xn, obj = ph1.W_array(), ph1.xbar_by_node()["ROOT"][0], ph1.nonant_values(), ph1._host("obj")
     sample = [0, 1, 2, 3, 500, 998, 999]
     o = oph.OraclePH([om.farmer("scen%d" % k, crops_multiplier=10, num_scens=S) for k in sample], rho=1.0)

@@ -9,7 +9,7 @@ the farmer/aircond goldens (test_oracle_golden.py)."""
 import numpy as np
 import pytest
 
-from helpers import all_certified, rel, run_engine
+from helpers import all_certified, kkt_recheck, rel, run_engine
 from mpisppy_amd.batch import from_models
 from mpisppy_amd.examples import netdes
 from oracle import models as om, ph as oph
@@ -79,6 +79,7 @@ def check_netdes_ph(lib, device, iters=3):
     o.solve_loop()
     assert rel(ph.nonant_values(), o.xn()) < 1e-6
     assert rel(ph._host("obj"), o.obj) < 1e-8
+    kkt_recheck(ph, tag="netdes")
     return ph, o
 
 

@@ -7,7 +7,7 @@ whose PH loop is pinned by the farmer/aircond goldens (test_oracle_golden.py).""
 import numpy as np
 import pytest
 
-from helpers import all_certified, rel, run_engine
+from helpers import all_certified, kkt_recheck, rel, run_engine
 from mpisppy_amd.batch import from_models
 from mpisppy_amd.examples import sslp
 from oracle import models as om, ph as oph
@@ -64,6 +64,7 @@ def check_sslp_ph(lib, device, iters=3):
     assert rel(ph.nonant_values(), o.xn()) < 1e-6
     eng_obj = ph._host("obj")
     assert rel(eng_obj, o.obj) < 1e-8
+    kkt_recheck(ph, tag="sslp")
     return ph, o
 
 

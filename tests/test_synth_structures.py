@@ -15,7 +15,7 @@ import pytest
 
 import synth_cases as sc
 import xhat_cases as xc
-from helpers import all_certified, oracle_continue_from, rel, run_engine
+from helpers import all_certified, kkt_recheck, oracle_continue_from, rel, run_engine
 from oracle import ph as oph
 
 SEEDS = (1, 2)
@@ -103,7 +103,7 @@ def host_recheck(ph, fam, exact=True):
     certificate's tolerance, as oracle/qp.py states it), and the returned objective
     equal to c'x + c0 + W'x_N + sum rho/2 (x_N - x-bar)^2 recomputed from x, W, rho and
     x-bar to 1e-12 relative.  exact: math.fsum per scenario; else vectorised numpy (the
-    large batches)."""
+    large batches).  Then the row duals of the same solve (helpers.kkt_recheck)."""
     x = ph._host("x")                                  # (n, S)
     S, N = fam.S, fam.N
     W, rho, xb, obj = ph.W_array(), ph._host("rho").T, engine_xbar(ph, fam), ph._host("obj")
@@ -127,6 +127,7 @@ def host_recheck(ph, fam, exact=True):
     print(fam.family, "host recheck: violation %.2e objective %.2e" % (viol, oerr))
     assert viol <= 1e-9
     assert oerr <= 1e-12
+    kkt_recheck(ph, tag=fam.family)
     return viol, oerr
 
 
@@ -239,6 +240,10 @@ def check_paths(lib, device, fam, paths=PATHS):
     assert not hasattr(out["host_loop"][0], "iterk_stats")
     st = out["starved"][0]
     assert st.iterk_stats["stragglers"] + sum(r.get("stragglers", 0) for r in st.solve_stats) > 0
+    # the row duals of every path's last solve (the starved path's: written by the tier
+    # that finished its lanes)
+    for name, res in out.items():
+        kkt_recheck(res[0], tag="%s %s" % (fam.family, name))
     return out
 
 
@@ -259,6 +264,7 @@ def check_beyond_limits(lib, device, fam, so=None, want="off: size"):
     served["pdhg"] = sum(s["pdhg_iters"] for s in ph.solve_stats)
     print(fam.flags["n"], fam.flags["m"], fam.flags["nnz"], info, served)
     assert served["lane_certified"] == 0
+    kkt_recheck(ph, tag="%s %s" % (fam.family, so))
     return ph, served
 
 
