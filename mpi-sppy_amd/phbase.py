@@ -492,8 +492,8 @@ class PHBase(SPOpt):
         self._save_original_nonants()
         self._PHIter = 0
         self._create_solvers()
-        self.solve_loop(solver_options=self.current_solver_options, gripe=True, tee=False,
-                        verbose=self.options["verbose"])
+        so0 = self.current_solver_options
+        self.solve_loop(solver_options=so0, gripe=True, tee=False, verbose=self.options["verbose"])
         if not self._solve_pending:
             # already final (nothing left to adopt): Iter0's objectives / statuses now
             self._iter0_obj_dev.copy_(self._obj)
@@ -504,7 +504,24 @@ class PHBase(SPOpt):
         self.conv = None
         self.reenable_W_and_prox()
         self.current_solver_options = self.options["iterk_solver_options"]
-        return None
+        if not self._solve_pending and not self._iter0_on_lane_path(so0):
+            # the generic path's solve (the workgroup, sparse and PDHG tiers; a lane
+            # solve that was not deferred): final, with its host wait behind it, and
+            # nothing phx_iterk would adopt -- it would run every iteration before
+            # the checks saw an infeasible scenario.  The reference quits right
+            # after Iter0 (phbase.py:812-823), so the checks run now
+            self._resolve_deferred_iter0()
+        return self.trivial_bound
+
+    def _iter0_on_lane_path(self, solver_options):
+        """Iter0's solve, just enqueued by _iter0_deferred_start, is the lane solver's
+        deferred solve: the one phx_iterk adopts (the host emulation finishes such a
+        solve at once and still reports it adopted)."""
+        info = getattr(self, "_jit_info", None)
+        if info is None:
+            info = self._jit_info = self._native.jit_info(self._ctx).decode()
+        return bool(getattr(self, "_last_solve_deferred", False) and info.startswith("on")
+                    and int(self._solve_opts(solver_options).lane_solver))
 
     def _native_loop_ok(self):
         """The device-driven loop (phx_iterk) runs the same iterations when no

@@ -199,6 +199,7 @@ class SPOpt(SPBase):
         defer = (self.extensions is None and not dtiming and so.lane_solver and self._bundles is None
                  and self._prox_lin is None and bool((solver_options or {}).get("defer", 1)))
         so.defer = 1 if defer else 0
+        self._last_solve_deferred = bool(defer)
         self._set_ph_terms()
         total = ctypes.c_int32(0)
         t0 = time.perf_counter()

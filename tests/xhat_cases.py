@@ -223,10 +223,10 @@ def check_try_one(ev, model, size, donor_dicts, lane=False, sample=None, scens=N
     return xb, o
 
 
-def check_restored_solve(ev, before, lane=False):
+def check_restored_solve(ev, before, lane=False, solver_options=None):
     """After phx_fix_nonants(NULL) a plain solve returns the pre-trial nonants."""
     ev._restore_nonants_device()
-    ev.solve_loop()
+    ev.solve_loop(solver_options=solver_options)
     assert rel(ev.nonant_values(), before) < 1e-9
     if lane:
         st = last_stats(ev)
