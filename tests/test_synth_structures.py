@@ -257,7 +257,9 @@ def check_beyond_limits(lib, device, fam, so=None, want="off: size"):
     """A family the lane solver does not serve: the reason, the oracle's trajectory on
     the generic tiers (host loop: per-solve statistics), and which tier certified."""
     so = dict(so or {}, native_loop=0)
-    ph = check_vs_oracle(lib, device, fam, so)[0]
+    res = check_vs_oracle(lib, device, fam, so)
+    ph = res[0]
+    ph.main_result = res[1:]                           # (conv, E[obj], trivial bound) of this run
     info = ph._native.jit_info(ph._ctx).decode()
     assert info.startswith(want), info
     served = {k: sum(s[k] for s in ph.solve_stats) for k in ("wg_certified", "sp_certified", "lane_certified")}
