@@ -362,6 +362,68 @@ int phx_norm_rho(phx_ctx* ctx, const phx_tree_desc* tree, const phx_norm_rho_opt
 int phx_rho_sums(phx_ctx* ctx, const double* rho, const double* prob, const double* xbar_node,
                  const double* xbar_prev, const int32_t* xbar_idx, double* out, void* stream);
 
+/* Cost-proportional rho (the Watson-Woodruff rule), local part: the statistics
+ * of the per-scenario rho candidates of every (node, slot) entry.  For nonant
+ * slot j, local scenario s and e = xbar_idx[j*S+s] the candidate is
+ *     r = |cost[j*S+s]| / d        (IEEE division; cost is a [N][S] slot array)
+ * with
+ *   denom_node given ([NNS]):  d = denom_node[e], the reference's
+ *     scenario-independent denominator max(1/rho_relative_bound, sum_s
+ *     prob_coeff*|x - xbar|) (Find_Rho._grad_denom, utils/find_rho.py:118-147).
+ *     The caller forms it with phx_node_absdev (wt = prob_coeff per slot), one
+ *     all-reduce and a clamp.  scen_denom_out is not touched (may be NULL).
+ *   denom_node NULL:  d = scen_denom[s] = max over ALL nonant slots j of
+ *     max(|x - xbar|, 2*(x - xbar)^2), ONE scalar per scenario over both forms
+ *     and every slot: what np.max((w_denom, prox_denom)) evaluates in
+ *     Find_Rho.compute_rho (utils/find_rho.py:78-115, :189-191; not a per-slot
+ *     denominator -- the reference's pinned values depend on it).  Written to
+ *     scen_denom_out [S].
+ * d == 0 gives r = +inf whatever the cost (a zero cost too: no 0/0), so no NaN
+ * enters a reduction from finite inputs; a zero cost gives r = 0 otherwise.
+ * out is [4*NNS], laid out [sum | count | max | -min], each over the entry's
+ * local scenarios: the sum in a fixed order (the Compute_Xbar tiles of `tree`,
+ * tiles in tile order within a node: two calls agree bit for bit), count the
+ * node's local scenarios as a double, max and -min exact.  Entries of nodes
+ * absent locally read 0, 0, -inf, -inf, so the caller SUM-all-reduces the
+ * first 2*NNS doubles and MAX-all-reduces the last 2*NNS with no special case.
+ * Replaces the per-scenario Python loops, the gather to rank 0 and the
+ * np.divide of Find_Rho.compute_rho (utils/find_rho.py:170-204).
+ * `partial` is a caller-owned buffer of 2*tree->npart doubles of its own.   */
+int phx_cost_rho_stats(phx_ctx* ctx, const phx_tree_desc* tree, const double* cost, const double* x,
+                       const double* xbar_node, const int32_t* xbar_idx, const double* denom_node,
+                       double* partial, double* scen_denom_out, double* out, void* stream);
+
+/* The order statistic of the rule (--order-stat; Find_Rho._order_stat,
+ * utils/find_rho.py:150-168): 0 the min, 0.5 the mean, 1 the max.           */
+typedef struct phx_cost_rho_opts {
+    double order_stat;
+} phx_cost_rho_opts;
+
+/* Cost-proportional rho, second part: from the all-reduced statistics
+ * (phx_cost_rho_stats' layout) every entry e < NNS takes mean = sum/count and
+ * Find_Rho._order_stat with its association (a = order_stat, in [0, 1]):
+ *     a == 0.5   rho_e = mean
+ *     a <  0.5   rho_e = min + a*2*(mean - min)
+ *     a >  0.5   rho_e = (2*mean - max) + a*2*(max - mean)
+ * rho_node_out[e] = rho_e.  Where count == 0 or rho_e is not finite,
+ * kept_out[e] = 1 and the entry's rho is left untouched (the reference would
+ * install inf or nan there: a deliberate departure); else kept_out[e] = 0 and
+ * rho[j][s] = rho_e for every local (j, s) with xbar_idx[j*S+s] == e.  A cost of
+ * 0 gives rho 0, as in the reference.  Every rank takes the same decisions from
+ * the same statistics.  Replaces the CSV round trip and the per-(scenario,
+ * nonant) rho writes of Gradient_extension.miditer (extensions/
+ * gradient_extension.py:86-94) and Set_Rho.rho_setter (utils/find_rho.py:231-259).
+ * rho_node_out [NNS] doubles, kept_out [NNS] int32.                         */
+int phx_cost_rho_apply(phx_ctx* ctx, const phx_tree_desc* tree, const phx_cost_rho_opts* opts,
+                       const double* stats, const int32_t* xbar_idx, double* rho,
+                       double* rho_node_out, int32_t* kept_out, void* stream);
+
+/* out[0] = sum over the local [N][S] of |W - W_prev|, slots in order within a
+ * scenario, scenarios in a fixed two-level order (as phx_rho_sums), and W_prev
+ * overwritten with W in the same pass.  The local part of WTracker.W_diff
+ * (utils/wtracker.py), which Gradient_extension's trigger reads.            */
+int phx_w_absdiff(phx_ctx* ctx, const double* W, double* W_prev, double* out, void* stream);
+
 /* Scenario-major export of a [N][S] slot array (W or nonant x) into
  * out[S*N + 0..] — the flat layout of PHBase._populate_W_cache /
  * PHHub.send_nonants (phbase.py:346-366, hub.py:562-577).                  */

@@ -107,6 +107,10 @@ class NormRhoOpts(ctypes.Structure):
     ]
 
 
+class CostRhoOpts(ctypes.Structure):
+    _fields_ = [("order_stat", c_double)]
+
+
 # every symbol of include/phx.h (tests check the library exports all of them)
 SYMBOLS = [
     "create", "destroy", "last_error", "build_info", "set_problem", "set_bounds", "set_ph_terms",
@@ -114,6 +118,7 @@ SYMBOLS = [
     "iterk", "iterk_prepare", "comm_unique_id", "set_comm", "debug_spd_inverse",
     "node_absdev", "norm_rho", "rho_sums", "donor_gather", "fix_nonants",
     "fixer_step", "fix_nonants_where",
+    "cost_rho_stats", "cost_rho_apply", "w_absdiff",
 ]
 
 
@@ -184,6 +189,13 @@ class Lib:
                               c_void_p, c_double, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
         self.fix_nonants_where = fn("fix_nonants_where", ctypes.c_int,
                                     [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+        self.cost_rho_stats = fn("cost_rho_stats", ctypes.c_int,
+                                 [c_void_p, ctypes.POINTER(TreeDesc), c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+        self.cost_rho_apply = fn("cost_rho_apply", ctypes.c_int,
+                                 [c_void_p, ctypes.POINTER(TreeDesc), ctypes.POINTER(CostRhoOpts), c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+        self.w_absdiff = fn("w_absdiff", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
 
     def check(self, ctx, rc, what):
         if rc != 0:
