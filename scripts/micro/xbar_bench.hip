@@ -8,7 +8,8 @@ __global__ __launch_bounds__(RED_NT) void v_tiles(int S, const int32_t* tile_s0,
     const int32_t* tile_slot, const int32_t* tile_nlen, const int32_t* tile_out, const int32_t* slot_col,
     const double* x, const double* pc, double* partial) {
     __shared__ double sh[RED_NT / 64 * 2 * XB_CH];
-    xbar_tile(blockIdx.x, S, tile_s0, tile_s1, tile_slot, tile_nlen, tile_out, slot_col, x, pc, partial, sh);
+    tile_pass(XbarOp{S, 0, slot_col, x, pc, nullptr}, TileMap{tile_s0, tile_s1, tile_slot, tile_nlen, tile_out},
+              NodeMap{}, (int)blockIdx.x, 0, 1, partial, sh);
 }
 // variant: loads only, one store per thread
 __global__ __launch_bounds__(RED_NT) void v_loads(int S, const int32_t* slot_col, const double* x, const double* pc,

@@ -51,11 +51,17 @@ def test_weighted_case_gpu(gpu_lib, key, mode):
     """S = 70: checks B, C and D.  Two-stage trees: the default loop is fused
     (phx_lane_warm_fz1), iterk_fused 0 is not (k_small_xw); the three-stage tree is never
     fused and is held to the oracle and the recheck all the same.  Iter0 is deferred
-    (k_iter0_keep1 forms the trivial bound) in the probabilities-only runs only."""
+    (k_iter0_keep1 forms the trivial bound) in the probabilities-only runs only; its
+    sums equal phx_expect's on the kept objectives and statuses bit for bit."""
     cs = wc.case(key, mode)
     first_context(gpu_lib, cs)
     t0 = time.perf_counter()
-    wc.check_case(gpu_lib, None, cs, fused=cs.base.bf is None)
+    runs = wc.check_case(gpu_lib, None, cs, fused=cs.base.bf is None)[0]
+    if mode == "p":
+        # k_iter0_keep1's sums are phx_expect's (k_expect) bit for bit on what it kept
+        left, again = runs[wc.ITERS]["iter0_exp"]
+        print("%s/%s adopted Iter0 expectations %r, phx_expect %r" % (key, mode, left.tolist(), again.tolist()))
+        assert np.array_equal(left, again)
     print("%s/%s: %.1f s" % (key, mode, time.perf_counter() - t0))
 
 
@@ -86,7 +92,8 @@ def test_s1100_fused_and_unfused_gpu(gpu_lib):
 def test_s8200_adopted_iter0_gpu(gpu_lib):
     """S = 8,200, probabilities only, default options: the adopted Iter0's sum p obj
     (k_iter0_keep: chunked, last-block fold) against math.fsum over the engine's own
-    Iter0 objectives to 1e-12, its total probability likewise, and check C."""
+    Iter0 objectives to 1e-12, its total probability likewise, and check C.  The three
+    sums equal phx_expect's on the kept objectives and statuses bit for bit."""
     cs = wc.case("vary_all", "p", S=8200)
     first_context(gpu_lib, cs)
     runs = wc.prefix_runs(gpu_lib, None, cs, creator=cs.fam.batch_creator_fn(), K=3)
@@ -95,6 +102,11 @@ def test_s8200_adopted_iter0_gpu(gpu_lib):
     for k, r in enumerate(runs):
         if k:
             assert r["deferred"] and r["stats"]["fused"], r["stats"]
+            # k_iter0_keep's sums (9 blocks) are phx_expect's (k_expect_part, k_expect_fold)
+            # bit for bit on what it kept
+            left, again = r["iter0_exp"]
+            print("S = 8200 run %d adopted Iter0 expectations %r, phx_expect %r" % (k, left.tolist(), again.tolist()))
+            assert np.array_equal(left, again), k
         tb = math.fsum(cs.p * r["iter0_obj"]) + math.fsum(cs.p * cs.fam.c0)
         print("S = 8200 run %d: deferred %s trivial bound %.15g host %.15g (relative %.1e) E1 - 1 = %.1e"
               % (k, r["deferred"], r["tb"], tb, abs(r["tb"] - tb) / max(1.0, abs(tb)), r["E1"] - 1.0))

@@ -204,17 +204,28 @@ def run(lib, device, cs, iters, so=None, creator=None, extension=False, mpicomm=
     return ph, conv, Eobj, tb
 
 
+def iter0_expectations(ph):
+    """(what the loop left in the pinned Iter0 expectations, phx_expect on the kept Iter0
+    objectives and statuses into a fresh buffer), both [3] float64."""
+    lib = ph._native
+    again = torch.full((3,), np.nan, dtype=torch.float64, device=ph.device)
+    lib.check(ph._ctx, lib.expect(ph._ctx, ph._prob.data_ptr(), ph._iter0_obj_dev.data_ptr(),
+                                  ph._iter0_status_dev.data_ptr(), again.data_ptr(), ph._stream()), "expect")
+    return ph._iter0_exp_host.numpy().copy(), again.cpu().numpy()
+
+
 def snapshot(cs, ph, conv, Eobj, tb, keep_x=False):
     """What the checks read of a run, as host arrays (the PH object is not kept)."""
     N, S = cs.N, cs.S
     st = getattr(ph, "iterk_stats", None)
+    deferred = bool(getattr(ph, "_iter0_was_deferred", False))
     return dict(
         xn=ph.nonant_values(), W=ph.W_array(), xb=ph.xbar_by_node(), conv=conv, Eobj=Eobj, tb=tb,
         obj=ph._host("obj").copy(), x=ph._host("x").copy() if keep_x else None,
         pc=ph._pc.view(N, S).cpu().numpy().T.copy(), pc_host=ph._prob_coeff.T.copy(), rho=ph._host("rho").T.copy(),
         loc=np.asarray(ph.batch.nonant.slot_local), iters=ph._PHIter, certified=all_certified(ph),
         stats=None if st is None else dict(st), solve_stats=[dict(s) for s in ph.solve_stats],
-        deferred=bool(getattr(ph, "_iter0_was_deferred", False)), E1=getattr(ph, "E1", None),
+        deferred=deferred, E1=getattr(ph, "E1", None), iter0_exp=iter0_expectations(ph) if deferred else None,
         iter0_obj=ph._iter0_obj.copy(), jit=ph._native.jit_info(ph._ctx).decode())
 
 
