@@ -621,6 +621,44 @@ typedef struct phx_iterk_result {
 int phx_iterk(phx_ctx* ctx, const phx_solve_opts* opts, const phx_iterk_args* args,
               phx_iterk_result* result_host, void* stream);
 
+/* phx_iterk with NormRhoUpdater.miditer's update (norm_rho_updater.py:112-143)
+ * inside the loop: per iteration k, between Update_W / convergence_diff and the
+ * solve (the reference's miditer, phbase.py:914-926),
+ *     k > stop_after_iter >= 0       nothing
+ *     else have_prev == 0            xbar_prev = x-bar_k (the first miditer of a run)
+ *     else                           phx_node_absdev (wt = prob) into primal,
+ *                                    [the in-place all-reduce of primal[0..NNS],
+ *                                    args->allreduce or the context's communicator,]
+ *                                    phx_norm_rho's rule and scale with
+ *                                    allow_decrease = (k >= decrease_from_iter)
+ * so solve k runs with the new rho on every solver tier.  args->rho is WRITTEN
+ * by this call (phx_iterk only reads it).  The iteration that converges still
+ * runs its update (miditer comes before the stop test); an iteration stopped for
+ * leftover lanes runs it once, when it is enqueued again; iterations past a stop
+ * run none, but with several ranks still issue the all-reduce, so every rank
+ * issues the same collectives.  The fused one-launch-per-iteration mode is off
+ * (result->fused = 0): the rule needs x-bar_k reduced over the grid before solve
+ * k reads rho.  The residuals, the rule and the scale are phx_node_absdev's and
+ * phx_norm_rho's, bit for bit.                                               */
+typedef struct phx_iterk_rho {
+    phx_norm_rho_opts opts;        /* allow_decrease is ignored: derived per iteration */
+    int32_t decrease_from_iter;    /* iterations_converged_before_decrease             */
+    int32_t stop_after_iter;       /* rho_update_stop_iterations; < 0: never           */
+    int32_t have_prev;             /* in/out: xbar_prev holds a snapshot               */
+    const double* prob;            /* [S] scenario probabilities (phx_node_absdev's wt) */
+    double* partial;               /* [tree->npart], the caller's own                  */
+    double* primal;                /* [NNS+1] device; the buffer that is all-reduced   */
+    double* xbar_prev;             /* [NNS]                                            */
+    double* dual_out;              /* [NNS] or NULL                                    */
+    int32_t* action_out;           /* [NNS]: the last update's actions                 */
+    int32_t* action_log;           /* [max_iters][NNS] or NULL: the actions of iteration k in
+                                      row k-1 (rows of iterations without an update untouched) */
+    int32_t updates;               /* out: updates applied (snapshot-only iterations not counted) */
+} phx_iterk_rho;
+
+int phx_iterk_norm_rho(phx_ctx* ctx, const phx_solve_opts* opts, const phx_iterk_args* args,
+                       phx_iterk_rho* rho_args, phx_iterk_result* result_host, void* stream);
+
 /* The context's own collective for phx_iterk: an RCCL communicator over the
  * ranks of the PH cylinder (one process per GPU), so the per-iteration
  * all-reduce of the fused node buffer is enqueued by phx_iterk itself

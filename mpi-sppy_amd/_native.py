@@ -107,6 +107,16 @@ class NormRhoOpts(ctypes.Structure):
     ]
 
 
+class IterkRho(ctypes.Structure):
+    _fields_ = [
+        ("opts", NormRhoOpts), ("decrease_from_iter", c_int32), ("stop_after_iter", c_int32),
+        ("have_prev", c_int32),
+        ("prob", c_void_p), ("partial", c_void_p), ("primal", c_void_p), ("xbar_prev", c_void_p),
+        ("dual_out", c_void_p), ("action_out", c_void_p), ("action_log", c_void_p),
+        ("updates", c_int32),
+    ]
+
+
 class CostRhoOpts(ctypes.Structure):
     _fields_ = [("order_stat", c_double)]
 
@@ -119,6 +129,7 @@ SYMBOLS = [
     "node_absdev", "norm_rho", "rho_sums", "donor_gather", "fix_nonants",
     "fixer_step", "fix_nonants_where",
     "cost_rho_stats", "cost_rho_apply", "w_absdiff",
+    "iterk_norm_rho",
 ]
 
 
@@ -196,6 +207,9 @@ class Lib:
                                  [c_void_p, ctypes.POINTER(TreeDesc), ctypes.POINTER(CostRhoOpts), c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
         self.w_absdiff = fn("w_absdiff", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p])
+        self.iterk_norm_rho = fn("iterk_norm_rho", ctypes.c_int,
+                                 [c_void_p, ctypes.POINTER(SolveOpts), ctypes.POINTER(IterkArgs),
+                                  ctypes.POINTER(IterkRho), ctypes.POINTER(IterkResult), c_void_p])
 
     def check(self, ctx, rc, what):
         if rc != 0:

@@ -12,6 +12,10 @@
 //     k_sums_fold): phx_expect, phx_rho_sums, phx_w_absdiff, Iter0's keep
 //     kernels -- terms ExpectTerm, RhoTerm, WAbsdiffTerm.
 // All reductions are fixed-order trees (no float atomics).
+// The norm-rho update inside the device loop (phx_iterk_norm_rho) adds no
+// reduction: its kernels are the absdev passes, the rule and the scale under a
+// gate of their own (rho_gated), the rule evaluated by the block that holds
+// every entry when the residuals need no all-reduce.
 #pragma once
 
 // ---- block reduction helpers (wave shuffles + LDS, fixed order) ----
@@ -965,8 +969,9 @@ struct AbsdevSmall {
 };
 // dynamic LDS: [run sums NNS x SX_WAVES | entry sums NNS]
 static size_t absdev_small_lds(int NNS) { return sizeof(double) * (size_t)NNS * (SX_WAVES + 1); }
-__global__ __launch_bounds__(SX_NT) void k_absdev_small(AbsdevSmall a) {
-    extern __shared__ double ad_lds[];
+// (the pass itself: k_absdev_small, and k_absdev_small_rho of the device loop;
+// returns the entry sums in LDS, valid in every thread)
+__device__ __forceinline__ const double* absdev_small_pass(const AbsdevSmall& a, double* ad_lds) {
     double* s_runs = ad_lds;
     double* s_out = ad_lds + (size_t)a.NNS * SX_WAVES;
     const int s = (int)threadIdx.x, lane = s & 63, wv = s >> 6;
@@ -1028,6 +1033,11 @@ __global__ __launch_bounds__(SX_NT) void k_absdev_small(AbsdevSmall a) {
         for (int e = 0; e < a.NNS; ++e) tot += s_out[e];
         a.out[a.NNS] = tot;
     }
+    return s_out;
+}
+__global__ __launch_bounds__(SX_NT) void k_absdev_small(AbsdevSmall a) {
+    extern __shared__ double ad_lds[];
+    absdev_small_pass(a, ad_lds);
 }
 
 // phx_node_absdev above that: k_xbar's layout (tile_pass / fold_all) -- the
@@ -1063,28 +1073,37 @@ struct AbsdevOp {
     __device__ void store(int e, const double (&r)[1], double) const { out[e] = r[0]; }
 };
 
-__global__ __launch_bounds__(RED_NT) void k_absdev(
-    int S, int ntiles, const int32_t* tile_s0, const int32_t* tile_s1, const int32_t* tile_slot,
-    const int32_t* tile_nlen, const int32_t* tile_out, const int32_t* slot_col, const double* x,
-    const double* xbar, const double* wt, int per_slot, double* partial, int nnodes,
-    const int32_t* node_tile_ptr, const int32_t* node_off, const int32_t* node_nlen, int NNS, double* out,
-    unsigned int* ticket) {
-    __shared__ double sh[RED_NT / 64 * XB_CH];
-    const AbsdevOp op{S, per_slot, slot_col, x, xbar, wt, out};
-    const NodeMap Nd{nnodes, node_tile_ptr, node_off, node_nlen, tile_out};
+struct AbsdevTiles {
+    int S, ntiles, nnodes, NNS, per_slot;
+    const int32_t *tile_s0, *tile_s1, *tile_slot, *tile_nlen, *tile_out, *slot_col;
+    const int32_t *node_tile_ptr, *node_off, *node_nlen;
+    const double *x, *xbar, *wt;
+    double *partial, *out;
+    unsigned int* ticket;
+};
+// (the pass itself: k_absdev, and k_absdev_rho of the device loop; true in the
+// last block, once every entry and the total are stored)
+__device__ __forceinline__ bool absdev_tiles_pass(const AbsdevTiles& a, double* sh) {
+    const AbsdevOp op{a.S, a.per_slot, a.slot_col, a.x, a.xbar, a.wt, a.out};
+    const NodeMap Nd{a.nnodes, a.node_tile_ptr, a.node_off, a.node_nlen, a.tile_out};
     // the grid is ntiles x nch (xbar_grid): block b takes tile b % ntiles, chunk b / ntiles
-    const int nch = (int)gridDim.x / ntiles;
-    tile_pass(op, TileMap{tile_s0, tile_s1, tile_slot, tile_nlen, tile_out}, Nd, (int)blockIdx.x % ntiles,
-              (int)blockIdx.x / ntiles, nch, partial, sh);
-    if (!arrive_last(ticket, gridDim.x)) return;
-    fold_all(op, Nd, partial, sh);
+    const int nch = (int)gridDim.x / a.ntiles;
+    tile_pass(op, TileMap{a.tile_s0, a.tile_s1, a.tile_slot, a.tile_nlen, a.tile_out}, Nd,
+              (int)blockIdx.x % a.ntiles, (int)blockIdx.x / a.ntiles, nch, a.partial, sh);
+    if (!arrive_last(a.ticket, gridDim.x)) return false;
+    fold_all(op, Nd, a.partial, sh);
     __syncthreads();
     // the total in entry order (entries of absent nodes: the zeros of the fill before this launch)
     if (threadIdx.x == 0) {
         double tot = 0.0;
-        for (int e = 0; e < NNS; ++e) tot += out[e];
-        out[NNS] = tot;
+        for (int e = 0; e < a.NNS; ++e) tot += a.out[e];
+        a.out[a.NNS] = tot;
     }
+    return true;
+}
+__global__ __launch_bounds__(RED_NT) void k_absdev(AbsdevTiles a) {
+    __shared__ double sh[RED_NT / 64 * XB_CH];
+    absdev_tiles_pass(a, sh);
 }
 
 // The norm-rho rule (norm_rho_updater.py:98-104, :122-143), a thread per local
@@ -1095,18 +1114,33 @@ struct NormRhoRule {
     double tol, inc, dec, factor, cdec;
     int allow;
 };
-__global__ void k_norm_rho_rule(int nnodes, int N, int S, const int32_t* node_tile_ptr, const int32_t* node_off,
-                                const int32_t* node_nlen, const int32_t* tile_s1, const int32_t* tile_slot,
-                                NormRhoRule o, const double* primal, const double* xbar, double* prev,
-                                const double* rho, double* dual_out, int32_t* action_out) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int v = (int)(idx / N), l = (int)(idx % N);
-    if (v >= nnodes || l >= node_nlen[v]) return;
-    const int tl = node_tile_ptr[v + 1] - 1;
-    const int e = node_off[v] + l;
-    const double xb = xbar[e];
-    const double p = primal[e];
-    const double d = rho[ix(tile_slot[tl] + l, tile_s1[tl] - 1, S)] * fabs(xb - prev[e]);
+// where the rule finds its entries and leaves its results (log_row: the row of
+// the device loop's action log, or null)
+struct RhoRuleIO {
+    int nnodes, N, S;
+    const int32_t *node_tile_ptr, *node_off, *node_nlen, *tile_s1, *tile_slot;
+    const double* xbar;
+    double* prev;
+    const double* rho;
+    double* dual_out;
+    int32_t *action_out, *log_row;
+};
+// thread idx = v * N + l: the operands of slot l of local node v (e < 0: none)
+struct RhoRuleEntry { int e; double xb, prev, rho_rep; };
+__device__ __forceinline__ RhoRuleEntry rho_rule_load(const RhoRuleIO& io, int64_t idx) {
+    RhoRuleEntry r{-1, 0.0, 0.0, 0.0};
+    const int v = (int)(idx / io.N), l = (int)(idx % io.N);
+    if (v >= io.nnodes || l >= io.node_nlen[v]) return r;
+    const int tl = io.node_tile_ptr[v + 1] - 1;
+    r.e = io.node_off[v] + l;
+    r.xb = io.xbar[r.e];
+    r.prev = io.prev[r.e];
+    r.rho_rep = io.rho[ix(io.tile_slot[tl] + l, io.tile_s1[tl] - 1, io.S)];
+    return r;
+}
+__device__ __forceinline__ void rho_rule_apply(const RhoRuleIO& io, const NormRhoRule& o, const RhoRuleEntry& r,
+                                               double p) {
+    const double d = r.rho_rep * fabs(r.xb - r.prev);
     int act = 0;
     if (p > o.factor * d && p > o.tol) {
         act = 1;
@@ -1115,21 +1149,108 @@ __global__ void k_norm_rho_rule(int nnodes, int N, int S, const int32_t* node_ti
     } else if (p < o.tol && d < o.tol) {
         act = 3;
     }
-    action_out[e] = act;
-    if (dual_out) dual_out[e] = d;
-    prev[e] = xb;
+    io.action_out[r.e] = act;
+    if (io.log_row) io.log_row[r.e] = act;
+    if (io.dual_out) io.dual_out[r.e] = d;
+    io.prev[r.e] = r.xb;
+}
+__global__ void k_norm_rho_rule(RhoRuleIO io, NormRhoRule o, const double* primal) {
+    const RhoRuleEntry r = rho_rule_load(io, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    if (r.e >= 0) rho_rule_apply(io, o, r, primal[r.e]);
 }
 
 // rho[j][s] scaled by the action of its (node, slot) entry: IEEE multiply /
 // divide (:135, :139, :142 -- not a multiplication by a reciprocal)
-__global__ void k_norm_rho_scale(int64_t tot, const int32_t* xbar_idx, const int32_t* action, double inc,
-                                 double dec, double cdec, double* rho) {
-    const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void rho_scale_at(int64_t o, int64_t tot, const int32_t* xbar_idx, const int32_t* action,
+                                             double inc, double dec, double cdec, double* rho) {
     if (o >= tot) return;
     const int act = action[xbar_idx[o]];
     if (act == 0) return;
     const double r = rho[o];
     rho[o] = act == 1 ? r * inc : (act == 2 ? r / dec : r / cdec);
+}
+__global__ void k_norm_rho_scale(int64_t tot, const int32_t* xbar_idx, const int32_t* action, double inc,
+                                 double dec, double cdec, double* rho) {
+    rho_scale_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, tot, xbar_idx, action, inc, dec, cdec, rho);
+}
+
+// ---- the update inside the device loop (phx_iterk_norm_rho) ----
+// The reference's miditer sits between convergence_diff and the stop test
+// (phbase.py:914-926), so the update of iteration k runs while the loop
+// proceeds AND at the iteration that converged (ctl[0] == 1, ctl[1] == k); not
+// at a straggler stop (ctl[0] == 2: that iteration is enqueued again once the
+// leftovers are finished) and not past a stop (the padded iterations).  ctl is
+// written by launches before these (Update_W / k_conv of the same iteration),
+// so every block of a launch takes the same decision.
+struct RhoGate { const int32_t* ctl; int iter; };
+__device__ __forceinline__ bool rho_gated(const RhoGate& g) {
+    const volatile int32_t* c = g.ctl;
+    const int32_t f = c[0];
+    return f != 0 && !(f == 1 && c[1] == g.iter);
+}
+
+// The first miditer of a run: x-bar_k into the snapshot, nothing else.
+__global__ void k_rho_snapshot(RhoGate g, int NNS, const double* xbar, double* prev) {
+    if (rho_gated(g)) return;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < NNS) prev[e] = xbar[e];
+}
+
+// Entries of nodes absent locally (several ranks): residual 0 before the pass,
+// action 0 and dual 0 for the rule -- phx_node_absdev's and phx_norm_rho's fills.
+__global__ void k_rho_clear(RhoGate g, int NNS, double* primal, double* dual, int32_t* action, int32_t* log_row) {
+    if (rho_gated(g)) return;
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e > NNS) return;
+    primal[e] = 0.0;
+    if (e == NNS) return;
+    action[e] = 0;
+    if (log_row) log_row[e] = 0;
+    if (dual) dual[e] = 0.0;
+}
+
+// phx_node_absdev's pass under the gate.  rule (one rank: the residuals are
+// final without an all-reduce): the block that holds every entry -- the one
+// block of the small path, the last block of the tiled one, which folded them
+// -- evaluates the rule before it leaves, a thread per (node, slot) as
+// k_norm_rho_rule.  That launch was three threads behind a chain of five
+// dependent loads; here the small path issues the rule's loads with the pass's
+// own at entry (x-bar, the snapshot and rho are final before this launch: rho
+// is scaled by the launch after it, so rho_rep is read before any scale).
+__global__ __launch_bounds__(SX_NT) void k_absdev_small_rho(AbsdevSmall a, RhoGate g, int rule, RhoRuleIO io,
+                                                            NormRhoRule o) {
+    extern __shared__ double ad_lds[];
+    RhoRuleEntry pre{-1, 0.0, 0.0, 0.0};
+    const int64_t nent = rule ? (int64_t)io.nnodes * io.N : 0;
+    if ((int64_t)threadIdx.x < nent) pre = rho_rule_load(io, threadIdx.x);
+    if (rho_gated(g)) return;
+    const double* s_out = absdev_small_pass(a, ad_lds);
+    for (int64_t idx = threadIdx.x; idx < nent; idx += SX_NT) {
+        const RhoRuleEntry r = idx == (int64_t)threadIdx.x ? pre : rho_rule_load(io, idx);
+        if (r.e >= 0) rho_rule_apply(io, o, r, s_out[r.e]);
+    }
+}
+__global__ __launch_bounds__(RED_NT) void k_absdev_rho(AbsdevTiles a, RhoGate g, int rule, RhoRuleIO io,
+                                                       NormRhoRule o) {
+    __shared__ double sh[RED_NT / 64 * XB_CH];
+    if (rho_gated(g)) return;
+    if (!absdev_tiles_pass(a, sh) || !rule) return;
+    // (the entries were stored by this block's threads before the pass's barrier)
+    for (int64_t idx = threadIdx.x; idx < (int64_t)io.nnodes * io.N; idx += RED_NT) {
+        const RhoRuleEntry r = rho_rule_load(io, idx);
+        if (r.e >= 0) rho_rule_apply(io, o, r, a.out[r.e]);
+    }
+}
+// several ranks: the rule behind the all-reduce of the residuals
+__global__ void k_norm_rho_rule_gated(RhoGate g, RhoRuleIO io, NormRhoRule o, const double* primal) {
+    if (rho_gated(g)) return;
+    const RhoRuleEntry r = rho_rule_load(io, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    if (r.e >= 0) rho_rule_apply(io, o, r, primal[r.e]);
+}
+__global__ void k_norm_rho_scale_gated(RhoGate g, int64_t tot, const int32_t* xbar_idx, const int32_t* action,
+                                       double inc, double dec, double cdec, double* rho) {
+    if (rho_gated(g)) return;
+    rho_scale_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, tot, xbar_idx, action, inc, dec, cdec, rho);
 }
 
 // phx_rho_sums: scenario s's terms, slots in order (one block up to

@@ -21,7 +21,8 @@ An entry whose rho would not be finite keeps its rho (see utils/find_rho.py).
 No temporary files are written.  ``_display_rho_values`` prints as the
 reference's, when the run is verbose (it reads rho back).
 
-A per-iteration hook: runs with it use the host loop, as with NormRhoUpdater.
+A per-iteration hook: runs with it use the host loop (NormRhoUpdater's update
+is the one that runs inside the device loop).
 """
 import types
 

@@ -16,6 +16,13 @@ per PH iteration, with no device-to-host read unless ``verbose``:
 
 The next solve picks the new rho up through ``_set_ph_terms``.  W is not
 rescaled when rho changes (the reference does not either).
+
+A plain ``NormRhoUpdater`` that is not ``verbose`` does not keep the run on
+the host loop: ``PHBase._iterk_native`` hands these buffers to
+``phx_iterk_norm_rho``, which runs the same update inside the device loop
+ and leaves this object in the state ``miditer`` would have.
+A subclass that overrides a loop hook, ``verbose``, a ``MultiExtension`` or
+``iterk_solver_options {"native_loop": 0}`` keep the host loop.
 """
 import ctypes
 
@@ -50,6 +57,12 @@ ACTIONS = {1: "Increasing", 2: "Decreasing", 3: "Converged, Decreasing"}
 
 class NormRhoUpdater(Extension):
 
+    # set before ph_main: the device loop keeps every iteration's actions in
+    # action_log, int32 [PHIterLimit][NNS], row k-1 for iteration k (zeros where
+    # an iteration made no update); the host loop keeps no log
+    log_actions = False
+    action_log = None
+
     def __init__(self, ph):
         super().__init__(ph)
         self.ph = ph
@@ -82,6 +95,25 @@ class NormRhoUpdater(Extension):
     def _snapshot_avg(self, ph):
         self._prev_avg.copy_(ph._xbar_node)
         self._have_prev = True
+
+    def _iterk_rho_args(self, max_iterations):
+        """phx_iterk_rho over this object's buffers: what the device loop needs to
+        run miditer's update itself (PHBase._iterk_native)."""
+        ph = self.ph
+        r = _native.IterkRho()
+        r.opts = self._opts
+        r.decrease_from_iter = int(self._required_converged_before_decrease)
+        r.stop_after_iter = -1 if self._stop_iter_rho_update is None else int(self._stop_iter_rho_update)
+        r.have_prev = int(self._have_prev)
+        r.prob, r.partial = ph._prob.data_ptr(), self._partial.data_ptr()
+        r.primal, r.xbar_prev = self._primal.data_ptr(), self._prev_avg.data_ptr()
+        r.dual_out, r.action_out = self._dual.data_ptr(), self._action.data_ptr()
+        r.action_log = None
+        if self.log_actions:
+            self.action_log = torch.zeros((max(max_iterations, 1), max(ph.NNS, 1)), dtype=torch.int32,
+                                          device=ph.device)
+            r.action_log = self.action_log.data_ptr()
+        return r
 
     def pre_iter0(self):
         pass

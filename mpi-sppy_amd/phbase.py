@@ -529,7 +529,7 @@ class PHBase(SPOpt):
         o = self.options
         if self.ph_converger is not None or self.spcomm is not None:
             return False
-        if self.extensions is not None and self._ext_hooks_in_loop():
+        if self.extensions is not None and self._ext_hooks_in_loop() and self._norm_rho_in_loop() is None:
             return False
         if o["display_progress"] or o["verbose"] or o["display_convergence_detail"]:
             return False
@@ -558,6 +558,20 @@ class PHBase(SPOpt):
         if not isinstance(ext, Extension):
             return True
         return any(getattr(type(ext), h, None) is not getattr(Extension, h) for h in self._LOOP_HOOKS)
+
+    def _norm_rho_in_loop(self):
+        """The extension object when its per-iteration hook can run inside the
+        device loop (phx_iterk_norm_rho): a NormRhoUpdater whose loop hooks are
+        that class's own (a subclass that overrides miditer needs the host between
+        steps) and which is not verbose (its table reads device state back every
+        iteration).  None otherwise: a MultiExtension, any other extension."""
+        from .extensions.norm_rho_updater import NormRhoUpdater
+        ext = getattr(self, "extobject", None)
+        if not isinstance(ext, NormRhoUpdater) or ext._verbose:
+            return None
+        if any(getattr(type(ext), h, None) is not getattr(NormRhoUpdater, h) for h in self._LOOP_HOOKS):
+            return None
+        return ext
 
     def _device_loop_solver(self, so):
         """Which solve phx_iterk can run per iteration: the lane solver (jit on),
@@ -604,6 +618,7 @@ class PHBase(SPOpt):
     def _allreduce_cb(self):
         if getattr(self, "_ar_cb", None) is None:
             bufs = {self._node_stage.data_ptr(): self._node_stage, self._seg_sums.data_ptr(): self._seg_sums}
+            self._ar_bufs = bufs     # (phx_iterk_norm_rho's primal residuals are added by _iterk_native)
             comm = self.mpicomm
             dev = self.device
             ext = {}
@@ -665,9 +680,22 @@ class PHBase(SPOpt):
         else:
             a.iter0_prob = a.iter0_expect = a.iter0_expect_host = None
         res = _native.IterkResult()
+        ext = self._norm_rho_in_loop() if self.extensions is not None else None
         t0 = time.perf_counter()
-        lib.check(self._ctx, lib.iterk(self._ctx, ctypes.byref(so), ctypes.byref(a), ctypes.byref(res),
-                                       self._stream()), "iterk")
+        if ext is None:
+            lib.check(self._ctx, lib.iterk(self._ctx, ctypes.byref(so), ctypes.byref(a), ctypes.byref(res),
+                                           self._stream()), "iterk")
+            self._rho_updates = 0
+        else:
+            # NormRhoUpdater.miditer inside the loop, on the updater's own buffers
+            r = ext._iterk_rho_args(int(max_iterations))
+            if self.n_proc > 1 and not self._native_comm:
+                self._allreduce_cb()
+                self._ar_bufs[ext._primal.data_ptr()] = ext._primal
+            lib.check(self._ctx, lib.iterk_norm_rho(self._ctx, ctypes.byref(so), ctypes.byref(a), ctypes.byref(r),
+                                                    ctypes.byref(res), self._stream()), "iterk_norm_rho")
+            ext._have_prev = bool(r.have_prev)
+            self._rho_updates = int(r.updates)
         if deferred:
             if res.adopted and self._solve_pending:
                 # Iter0's solve, finished inside phx_iterk (phx_last_solve_stats: its statistics)
@@ -715,7 +743,7 @@ class PHBase(SPOpt):
                             "straggler_stops": int(res.straggler_stops), "stragglers": int(res.stragglers),
                             "not_optimal": int(res.not_optimal), "lane_warm_ms": float(res.warm_ms),
                             "warm_launches": int(res.warm_launches), "wall_s": wall,
-                            "fused": bool(res.fused)}
+                            "fused": bool(res.fused), "rho_updates": int(getattr(self, "_rho_updates", 0))}
         if res.not_optimal:
             stc = self._status.cpu().numpy()
             name = self.__class__.__name__
