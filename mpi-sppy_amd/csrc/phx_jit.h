@@ -381,14 +381,13 @@ inline std::string lane_kernel_source(const LaneStructure& L, int warm_waves = 1
          "  if (t < io.S) still = phx_lane::all_lane<PT, false, true>(io, t, rescue, pk);\n"
          "  phx_lane::compact_lane(still, t, io.lanes_out, io.count_out);\n"
          "}\n";
-    // phx_iterk fused mode, after the last enqueued iteration: the decision on
-    // its conv (the next warm launch's prologue does it otherwise)
+    // phx_iterk fused mode, after the last enqueued iteration: its shard
+    // partials added into the stage buffer and the decision on its conv (the
+    // next warm launch's prologue does both otherwise)
     // (and the copies the host reads after the drain, whether or not the loop
     // stopped earlier: as the copy dispatches they replace)
     o << "extern \"C\" __global__ void __launch_bounds__(64) phx_fz_tail(phx_lane::LaneIO io, phx_lane::TailCopy tc) {\n"
-         "  phx_lane::tail_copy(tc);\n"
-         "  if (phx_lane::gated(io.gate)) return;\n"
-         "  (void)phx_lane::fz_decide(io.fz, io.fz.iter);\n"
+         "  phx_lane::fz_tail<PT>(io, tc);\n"
          "}\n";
     o << "extern \"C\" __global__ void __launch_bounds__(64, 4) phx_lane_map(phx_lane::LaneIO io) {\n"
          "  if (phx_lane::gated(io.gate)) return;\n"

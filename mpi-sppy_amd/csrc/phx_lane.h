@@ -145,8 +145,13 @@ struct IterkProgress {
 // phbase.py:321-343), then solve k with the new W; the lane's
 // prob_coeff-weighted x and x^2 of solve k are the partial sums of iteration
 // k+1's Compute_Xbar (phbase.py:54-80).  Per-block partials are folded by the
-// last block of each arrival shard, then by the last shard, into the stage
-// buffer of iteration k+1.  The stop test on conv_k runs in the prologue of
+// last block of each arrival shard into one partial per shard; the <= 8 shard
+// partials are added, in shard order, by every block of the NEXT launch at its
+// entry (fz_shard_load / fz_shard_sum; the tail kernel after the last launch),
+// so no block of this launch waits for a second fold level.  Several ranks
+// (fold_top): the last shard adds them into the stage buffer of iteration
+// k+1, which the all-reduce needs in memory between the launches.  The stop
+// test on conv_k runs in the prologue of
 // the NEXT launch (after the all-reduce on several ranks), so solve k is
 // speculative: it writes the other output buffer set and is simply not
 // committed when conv_k < convthresh.
@@ -154,15 +159,21 @@ struct FusedW {
     int32_t on;
     int32_t iter;              // k
     int32_t first;             // first iteration of a pipeline segment: no decision on conv_{k-1}
-    double* stage;             // [2*nns sums | straggler count | R conv sums]: read as iteration k's,
-                               // overwritten by the last block with iteration k+1's
+    int32_t from_shards;       // iteration k's sums: 1 the previous launch's shard partials (set (k-1) & 1),
+                               // 0 the stage buffer (k_xbar's after a segment's start; every launch with fold_top)
+    int32_t fold_top;          // 1: the launch's last block folds the shard partials into stage (several ranks)
+    int32_t nb;                // blocks of the fused launches (the tail kernel runs one)
+    double* stage;             // [2*nns sums | straggler count | R conv sums]: iteration k's when read
+                               // (!from_shards); written with iteration k+1's by the last block (fold_top),
+                               // by the tail kernel, or by a stop in the prologue (what the host reads next)
     double* node_sums;         // published x-bar | xsqbar (block 0, once the iteration proceeds)
     int32_t nns;               // node-slot count (= nonant slots: one tree node)
     const double* x_prev;      // solve k-1's x [n][S]
     const double* pc;          // prob_coeff [N][S]
     int32_t* ctl;              // [0] stop flag (the gate of later kernels), [1] stop iteration
     IterkProgress* prog;
-    double* part;              // [gridDim.x * NV] block partials, then [TICKET_SHARDS * NV] shard partials
+    double* part;              // two sets by launch parity (fz_part_set), each [gridDim.x * NP] block partials,
+                               // then [TICKET_SHARDS * NP] shard partials; NP = 2 NS + 2
     unsigned int* tk;          // sharded arrival counters (TICKET_SET words)
     int32_t g, R;              // this rank's emulated-rank entry, emulated rank count
     const double* cnt;         // [R] element counts (convergence_diff's denominators)
@@ -2094,6 +2105,13 @@ __device__ __forceinline__ double load_wt(const double* p) {
 // counter serialises its atomics at ~12 ns each: 391 arrivals on one word cost
 // ~5 us); the last arriver of each shard adds to the top counter, whose last
 // arriver is the last block overall.  The last block resets every counter.
+// The fused PH kernels' fold (fz_fold) uses the shard counters the same way
+// (block b arrives at counter b % TICKET_SHARDS) but, on one rank, stops at
+// the shard level: the last arriver of a shard stores the shard's partial,
+// resets its own counter (the next user is the next launch) and returns; the
+// top counter is not touched, and the shard partials are added by the next
+// launch's blocks at entry.  Only its several-rank form (FusedW::fold_top)
+// goes on to the top counter as arrive_last does.
 #define TICKET_SHARDS 8
 #define TICKET_STRIDE 32                        // 128-B lines
 #define TICKET_SET ((TICKET_SHARDS + 1) * TICKET_STRIDE)
@@ -2131,6 +2149,14 @@ __device__ __forceinline__ double dpp_add(double v) {
     const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, ROWMASK, 0xf, false);
     return v + __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
 }
+// Lane l's value of v, uniform (l uniform; the lane need not be active).
+__device__ __forceinline__ double lane_get(double v, int l) {
+    // (readlane is 32-bit: a 64-bit argument would be truncated to its low half)
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u & 0xffffffffull), l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 __device__ __forceinline__ double wave_sum(double v) {
     v = dpp_add<0xB1, 0xf>(v);     // quad_perm [1,0,3,2]
     v = dpp_add<0x4E, 0xf>(v);     // quad_perm [2,3,0,1]
@@ -2138,18 +2164,14 @@ __device__ __forceinline__ double wave_sum(double v) {
     v = dpp_add<0x140, 0xf>(v);    // row_mirror: every lane of a row holds its sum
     v = dpp_add<0x142, 0xa>(v);    // row_bcast:15 into rows 1, 3
     v = dpp_add<0x143, 0xc>(v);    // row_bcast:31 into rows 2, 3: lane 63 holds the total
-    // (readlane is 32-bit: a 64-bit argument would be truncated to its low half)
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u & 0xffffffffull), 63);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), 63);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    return lane_get(v, 63);
 }
 
-// (one wavefront; vector stores)
-__device__ __forceinline__ void tail_copy(const TailCopy& tc) {
+// (one wavefront; vector stores)  seg = false: the caller stores seg_dst itself
+__device__ __forceinline__ void tail_copy(const TailCopy& tc, bool seg = true) {
     const int t = (int)threadIdx.x;
     if (tc.left_dst && t == 0) tc.left_dst[0] = *(const volatile int32_t*)tc.left_src;
-    if (tc.seg_dst)
+    if (tc.seg_dst && seg)
         for (int g = t; g < tc.nseg; g += (int)blockDim.x) tc.seg_dst[g] = tc.seg_src[g];
     if (tc.exp_dst && t < 3) tc.exp_dst[t] = tc.exp_src[t];
 }
@@ -2166,12 +2188,16 @@ __device__ __forceinline__ void publish_progress(IterkProgress* p, int iter, int
 // of each rank's mean |x - x-bar|, ranks in order); the stop test
 // (phbase.py:914-926).  Uniform over the grid: every block reads the same
 // numbers.  Block 0 publishes the decision.  true: stopped.
-__device__ __forceinline__ bool fz_decide(const FusedW& f, int it) {
-    const double* seg = f.stage + 2 * f.nns + 1;
+// seg: the R convergence sums in memory (the stage buffer's), or null: this
+// rank's sum `own` in entry g and zeros elsewhere -- what the stage buffer
+// holds on one rank, so the same additions.
+__device__ __forceinline__ double fz_conv(const FusedW& f, double own, const double* seg) {
     double tot = 0.0;
     for (int r = 0; r < f.R; ++r)
-        if (f.cnt[r] > 0) tot += seg[r] / f.cnt[r];
-    const double conv = tot / f.R;
+        if (f.cnt[r] > 0) tot += (seg ? seg[r] : (r == f.g ? own : 0.0)) / f.cnt[r];
+    return tot / f.R;
+}
+__device__ __forceinline__ bool fz_decide(const FusedW& f, int it, double conv) {
     const bool done = conv < f.thresh;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (done) {
@@ -2183,41 +2209,125 @@ __device__ __forceinline__ bool fz_decide(const FusedW& f, int it) {
     return done;
 }
 
+// The fused fold's values, NP = 2 NS + 2 per partial: [0, NS) the x sums,
+// [NS, 2 NS) the x^2 sums, [2 NS] the convergence sum, [2 NS + 1] the lanes
+// the solve left.  The count rides in the fold (each block's own count; small
+// integers, exact in doubles, so the solve's counter word to the bit): the
+// counter word itself is the next launch's `counts_next`, which that launch's
+// block 0 zeroes while its later blocks have yet to start.
+// Launch k writes partial set k & 1 and reads set (k - 1) & 1: blocks beyond
+// the first resident wave of launch k+1 start once its early blocks retire,
+// that is after these have stored launch k+1's partials -- into the other set,
+// so a late block still finds launch k's.  Set k & 1 is next written by
+// launch k+2, which starts after every block of launch k+1 has ended.
+__device__ __forceinline__ double* fz_part_set(const FusedW& f, int np, int it) {
+    return f.part + (int64_t)(it & 1) * ((int64_t)f.nb + TICKET_SHARDS) * np;
+}
+// Launch `it`'s shard partials, one value per lane (every lane of the
+// wavefront active): lane i of register u holds value (64 u + i) of the
+// [shard][NP] table, 0.0 past the last non-empty shard.
+template <int NP>
+__device__ __forceinline__ void fz_shard_load(const FusedW& f, int it, double* r) {
+    const unsigned nsh = (unsigned)f.nb < TICKET_SHARDS ? (unsigned)f.nb : TICKET_SHARDS;
+    const double* sp = fz_part_set(f, NP, it) + (int64_t)f.nb * NP;
+    PHX_UNROLL for (int u = 0; u < (TICKET_SHARDS * NP + 63) / 64; ++u) {
+        const unsigned i = 64u * u + threadIdx.x;
+        r[u] = i < nsh * NP ? load_wt(sp + i) : 0.0;
+    }
+}
+// Value e summed over the shards in order, uniform: the additions of the
+// two-level fold's last block (an absent shard adds +0.0, which changes no
+// bit of a sum that started from +0.0).
+template <int NP>
+__device__ __forceinline__ double fz_shard_sum(const double* r, int e) {
+    double a = 0.0;
+    PHX_UNROLL for (int q = 0; q < TICKET_SHARDS; ++q) a += lane_get(r[(q * NP + e) / 64], (q * NP + e) % 64);
+    return a;
+}
+// Iteration k's sums in[NP]: from the previous launch's shard partials sv
+// (fz_shard_load), or from the stage buffer.
+template <class PT>
+__device__ __forceinline__ void fz_inputs(const FusedW& f, const double* sv, double* in) {
+    constexpr int NS = PT::nslot() > 0 ? PT::nslot() : 1;
+    constexpr int NP = 2 * NS + 2;
+    if (f.from_shards) {
+        PHX_UNROLL for (int e = 0; e < NP; ++e) in[e] = fz_shard_sum<NP>(sv, e);
+    } else {
+        PHX_UNROLL for (int e = 0; e < NP; ++e) in[e] = 0.0;
+        PHX_UNROLL for (int t = 0; t < PT::nslot(); ++t) {
+            in[t] = f.stage[t];
+            in[NS + t] = f.stage[f.nns + t];
+        }
+        in[2 * NS] = f.stage[2 * f.nns + 1 + f.g];
+        in[2 * NS + 1] = f.stage[2 * f.nns];
+    }
+}
+// ... and into the stage buffer, in its layout (one thread)
+template <int NS>
+__device__ __forceinline__ void fz_store_stage(const FusedW& f, const double* in) {
+    PHX_UNROLL for (int t = 0; t < NS; ++t) {
+        f.stage[t] = in[t];
+        f.stage[f.nns + t] = in[NS + t];
+    }
+    f.stage[2 * f.nns] = in[2 * NS + 1];
+    for (int r = 0; r < f.R; ++r) f.stage[2 * f.nns + 1 + r] = r == f.g ? in[2 * NS] : 0.0;
+}
+
 // Prologue (block-uniform; before anything is written): the decision on
 // conv_{k-1}; then a previous solve that left lanes to the generic path stops
 // the pipeline at k (every rank sees the same all-reduced count) before W is
 // touched.  Block 0 publishes x-bar_k.
-__device__ bool fz_prologue(const LaneIO& io) {
+// in[NP] (fz_inputs): iteration k's sums as this block formed them.  A stop
+// leaves them in the stage buffer, where the host's next step reads them (the
+// last test's convergence sums; after the several-rank fold they are there
+// already) -- stored before the stop is published.
+template <class PT>
+__device__ bool fz_prologue(const LaneIO& io, const double* in) {
     const FusedW& f = io.fz;
-    if (!f.first && fz_decide(f, f.iter - 1)) return false;
-    if (f.stage[2 * f.nns] > 0.5) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
+    constexpr int NS = PT::nslot() > 0 ? PT::nslot() : 1;
+    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+    const double conv = f.first ? 0.0 : fz_conv(f, in[2 * NS], f.from_shards ? nullptr : f.stage + 2 * f.nns + 1);
+    const bool strag = in[2 * NS + 1] > 0.5;
+    if (f.from_shards && lead && ((!f.first && conv < f.thresh) || strag)) fz_store_stage<NS>(f, in);
+    if (!f.first && fz_decide(f, f.iter - 1, conv)) return false;
+    if (strag) {
+        if (lead) {
             f.ctl[1] = f.iter;
             *(volatile int32_t*)f.ctl = 2;
             publish_progress(f.prog, f.iter, 2, 0.0);
         }
         return false;
     }
-    if (blockIdx.x == 0)
-        for (int e = threadIdx.x; e < 2 * f.nns; e += blockDim.x) f.node_sums[e] = f.stage[e];
+    if (lead) {
+        PHX_UNROLL for (int t = 0; t < PT::nslot(); ++t) {
+            f.node_sums[t] = in[t];
+            f.node_sums[f.nns + t] = in[NS + t];
+        }
+    }
     return true;
 }
 
-// The fold of the lanes' partials v[2 NS + 1] (the wavefront's sums, then the
-// blocks' and the shards' in fixed orders).  Every lane of the block calls it.
+// The fold of the lanes' partials v[NP] (the wavefront's sums, then the
+// blocks' in a fixed order; v[2 NS + 1], the block's left-over count, comes in
+// uniform).  Every lane of the block calls it.  It ends with the shard's
+// partial stored by the shard's last arriver: the next launch's blocks (or the
+// tail kernel) add the shards, so the chain behind the launch's slowest
+// wavefront is one ticket and one fold level.  fold_top (several ranks): the
+// last shard goes on to add them into the stage buffer.
 template <class PT>
 __device__ void fz_fold(const LaneIO& io, double* v) {
     const FusedW& f = io.fz;
     constexpr int NS = PT::nslot() > 0 ? PT::nslot() : 1;
-    constexpr int NV = 2 * NS + 1;
+    constexpr int NV = 2 * NS + 1, NP = NV + 1;
     PHX_UNROLL for (int e = 0; e < NV; ++e) v[e] = wave_sum(v[e]);
     const unsigned nb = gridDim.x, b = blockIdx.x, k = b % TICKET_SHARDS;
     const unsigned nk = (nb - k + TICKET_SHARDS - 1) / TICKET_SHARDS;
     const unsigned nsh = nb < TICKET_SHARDS ? nb : TICKET_SHARDS;
-    double* shard_part = f.part + (int64_t)nb * NV;
+    double* part = fz_part_set(f, NP, f.iter);
+    double* shard_part = part + (int64_t)nb * NP;
     __shared__ unsigned s_state;
     if (threadIdx.x == 0) {
-        PHX_UNROLL for (int e = 0; e < NV; ++e) store_wt(&f.part[(int64_t)b * NV + e], v[e]);
+        PHX_UNROLL for (int e = 0; e < NP; ++e) store_wt(&part[(int64_t)b * NP + e], v[e]);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         PHX_HANDOFF_RELEASE();
         s_state = __hip_atomic_fetch_add(f.tk + k * TICKET_STRIDE, 1u, __ATOMIC_RELAXED,
@@ -2227,20 +2337,29 @@ __device__ void fz_fold(const LaneIO& io, double* v) {
     if (!s_state) return;
     PHX_HANDOFF_ACQUIRE();
     // last of shard k: blocks k, k+8, ... in order (4 blocks' loads in flight)
-    PHX_UNROLL for (int e = 0; e < NV; ++e) v[e] = 0.0;
+    PHX_UNROLL for (int e = 0; e < NP; ++e) v[e] = 0.0;
     for (unsigned i0 = threadIdx.x; i0 < nk; i0 += 4 * 64) {
-        double l[4][NV];
+        double l[4][NP];
         PHX_UNROLL for (int u = 0; u < 4; ++u) {
             const unsigned i = i0 + 64u * u;
-            PHX_UNROLL for (int e = 0; e < NV; ++e)
-                l[u][e] = i < nk ? load_wt(&f.part[(int64_t)(k + TICKET_SHARDS * i) * NV + e]) : 0.0;
+            PHX_UNROLL for (int e = 0; e < NP; ++e)
+                l[u][e] = i < nk ? load_wt(&part[(int64_t)(k + TICKET_SHARDS * i) * NP + e]) : 0.0;
         }
-        PHX_UNROLL for (int u = 0; u < 4; ++u) PHX_UNROLL for (int e = 0; e < NV; ++e) v[e] += l[u][e];
+        PHX_UNROLL for (int u = 0; u < 4; ++u) PHX_UNROLL for (int e = 0; e < NP; ++e) v[e] += l[u][e];
     }
-    PHX_UNROLL for (int e = 0; e < NV; ++e) v[e] = wave_sum(v[e]);
+    PHX_UNROLL for (int e = 0; e < NP; ++e) v[e] = wave_sum(v[e]);
     __syncthreads();
+    if (!f.fold_top) {
+        // (no drain, no ticket: the launch's end publishes the stores; the
+        // shard's counter is next added to by the next launch)
+        if (threadIdx.x == 0) {
+            PHX_UNROLL for (int e = 0; e < NP; ++e) store_wt(&shard_part[k * NP + e], v[e]);
+            f.tk[k * TICKET_STRIDE] = 0u;
+        }
+        return;
+    }
     if (threadIdx.x == 0) {
-        PHX_UNROLL for (int e = 0; e < NV; ++e) store_wt(&shard_part[k * NV + e], v[e]);
+        PHX_UNROLL for (int e = 0; e < NP; ++e) store_wt(&shard_part[k * NP + e], v[e]);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         PHX_HANDOFF_RELEASE();
         const bool last = __hip_atomic_fetch_add(f.tk + TICKET_SHARDS * TICKET_STRIDE, 1u, __ATOMIC_RELAXED,
@@ -2256,7 +2375,7 @@ __device__ void fz_fold(const LaneIO& io, double* v) {
     const int e = threadIdx.x;
     if (e < NV) {
         double a = 0.0;
-        for (unsigned q = 0; q < nsh; ++q) a += load_wt(&shard_part[q * NV + e]);
+        for (unsigned q = 0; q < nsh; ++q) a += load_wt(&shard_part[q * NP + e]);
         if (e < NS) f.stage[e] = a;
         else if (e < 2 * NS) f.stage[f.nns + (e - NS)] = a;
         else {
@@ -2265,6 +2384,31 @@ __device__ void fz_fold(const LaneIO& io, double* v) {
                 (double)__hip_atomic_load(io.count_out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+
+// The tail kernel behind the last enqueued launch (one wavefront): what the
+// next launch's prologue would have done with that launch's shard partials --
+// the shards added in order, into the stage buffer and the caller's
+// convergence sums, and the decision on the launch's conv -- and tail_copy.
+// Past a stop (gated) the stage buffer holds the stop's sums already.
+template <class PT>
+__device__ void fz_tail(const LaneIO& io, const TailCopy& tc) {
+    const FusedW& f = io.fz;
+    constexpr int NS = PT::nslot() > 0 ? PT::nslot() : 1;
+    constexpr int NP = 2 * NS + 2;
+    double sv[(TICKET_SHARDS * NP + 63) / 64], in[NP];
+    fz_shard_load<NP>(f, f.iter, sv);
+    const bool run = !gated(io.gate);
+    const bool fold = run && !f.fold_top;
+    PHX_UNROLL for (int e = 0; e < NP; ++e) in[e] = fz_shard_sum<NP>(sv, e);
+    if (fold) {
+        if (threadIdx.x == 0) fz_store_stage<NS>(f, in);
+        if (tc.seg_dst)
+            for (int g = threadIdx.x; g < tc.nseg; g += (int)blockDim.x) tc.seg_dst[g] = g == f.g ? in[2 * NS] : 0.0;
+    }
+    tail_copy(tc, !fold);
+    if (!run) return;
+    (void)fz_decide(f, f.iter, fz_conv(f, in[2 * NS], fold ? nullptr : f.stage + 2 * f.nns + 1));
 }
 
 // Iter0 seeding on the GPU (kernel phx_lane_seed, one wavefront per block):
@@ -2360,7 +2504,7 @@ template <class PT, bool CARRY = PHX_CARRY_DEF, bool PARK = false>
 __device__ __forceinline__ void warm_fused(const LaneIO& io) {
     const FusedW& f = io.fz;
     constexpr int NS = PT::nslot() > 0 ? PT::nslot() : 1;
-    constexpr int NV = 2 * NS + 1;
+    constexpr int NP = 2 * NS + 2;
     constexpr int NVA = PT::NMAX_V, NW = aset_words(PT::NMAX_N, PT::NMAX_M);
     const int sc = blockIdx.x * 64 + threadIdx.x;
     const bool live = sc < io.S;
@@ -2380,15 +2524,20 @@ __device__ __forceinline__ void warm_fused(const LaneIO& io) {
             pcv[t] = f.pc[o];
         }
     }
+    // (the previous launch's shard partials: loads like the others, dropped
+    // by a gated launch and by a segment's first, which reads the stage buffer)
+    double sv[(TICKET_SHARDS * NP + 63) / 64], in[NP];
+    fz_shard_load<NP>(f, f.iter - 1, sv);
     lane_stamp(io, 0);
     if (gated(io.gate)) return;
-    if (!fz_prologue(io)) return;
+    fz_inputs<PT>(f, sv, in);
+    if (!fz_prologue<PT>(io, in)) return;
     zero_next_counts(io.counts_next);
     lane_stamp(io, 1);
     // Update_W (phbase.py:293-318) and |x_{k-1} - x-bar_k| (convergence_diff)
     double xb[NS], dl = 0.0;
     PHX_UNROLL for (int t = 0; t < PT::nslot(); ++t) {
-        xb[t] = f.stage[t];
+        xb[t] = in[t];
         const double diff = xv[t] - xb[t];
         wv[t] = wv[t] + rv[t] * diff;
         if (live) PHX_OUT(const_cast<double*>(io.W)[(int64_t)t * S + sc], wv[t]);
@@ -2458,8 +2607,8 @@ __device__ __forceinline__ void warm_fused(const LaneIO& io) {
     }
     // the lane's x-bar partials (a certified lane's unscaled x as written) and
     // its convergence term
-    double v[NV];
-    PHX_UNROLL for (int e = 0; e < NV; ++e) v[e] = 0.0;
+    double v[NP];
+    PHX_UNROLL for (int e = 0; e < NP; ++e) v[e] = 0.0;
 #ifndef PHX_FZ_NO_LDS_KEEP
     PHX_UNROLL for (int t = 0; t < PT::nslot(); ++t) pcv[t] = fz_keep[t * 64 + threadIdx.x];
     dl = fz_keep[NS * 64 + threadIdx.x];
@@ -2475,6 +2624,7 @@ __device__ __forceinline__ void warm_fused(const LaneIO& io) {
     }
     lane_stamp(io, 3);
     compact_lane(still, sc, io.lanes_out, io.count_out);
+    v[2 * NS + 1] = (double)__popcll(__ballot(still));   // what compact_lane added to the counter
     lane_stamp(io, 4);
     fz_fold<PT>(io, v);
     lane_stamp(io, 5);
